@@ -6,23 +6,34 @@ One "step" = one complete fit_predict pass of the hot path over the synthetic wo
 objective -> log-density), inputs already resident in HBM when the timed region starts.
 Workload: BASELINE config 3 -- 1e6 cells x 50 dims Gaussian mixture, 5 000 landmarks, Matern52.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W untimed and K timed steps, and prints the headline line (`value`, `ms_per_step`, the
+timed step's own `roofline` and `stages_s`).  Everything else below -- the companion measurements, the parity check, the
+CPU baselines -- runs only with --full.  --dump-outputs DIR writes what the last timed step returned (DIR/log_density.npy,
+float64; see dump_outputs); with the same arguments the inputs are the same in every run.
+
+The k-means landmarks of the sklearn route are cached under build/bench_cache/ (keyed by the subsample's bytes, m, the
+seed and the scikit-learn version); build() fills the cache for the default config, so that a plain run does not spend a
+minute in k-means before its first step.
 
 N > 1: ONE model, its cells sharded over the N ranks -- one process per GPU, RCCL all-reduce of (loss, grad) per evaluation
 and of the preconditioner's Gram once per build; no collective touches the n x m buffer.  Default `"scaling": "strong"`: the
 1e6 cells of BASELINE config 3 IN TOTAL, split N ways -- at every N the workload is the one BASELINE.json names and north_star's
-">= 6x at 8 GPUs" is quoted on; `value` = 1e6 cells x steps / time.  The WEAK step (1e6 cells PER GPU, one model on N x 1e6
-cells) is measured in the same run and reported beside it under `weak_scaling`; `--scaling weak` makes it the headline instead.
+">= 6x at 8 GPUs" is quoted on; `value` = 1e6 cells x steps / time.  With --full the WEAK step (1e6 cells PER GPU, one model on
+N x 1e6 cells) is measured in the same run and reported beside it under `weak_scaling`; `--scaling weak` makes it the headline
+instead.
 Only the launcher's environment variables (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*) are used; the ranks' host sides talk
 over a Unix socket.
 
 Prints ONE JSON line on rank 0 (fields documented in DESIGN.md S6).  The K timed steps are PURE FLOAT64: every pass
 of the MAP solve streams the fp64 n x m buffer (MELLON_AMD_MIXED=0), so `value`, `ms_per_step`, `roofline` and
-`dtype` describe the reference's own precision.  Beside it, untimed by the contract but in the same process: the
-product default with its 32-bit fixed-point surrogate passes (`ms_per_step_mixed`, `roofline_mixed_passes`) and the
-host-to-host fp64 step (`ms_per_step_host_to_host`, x uploaded inside the step).
+`dtype` describe the reference's own precision.  With --full, beside it, untimed by the contract but in the same process:
+the product default with its 32-bit fixed-point surrogate passes (`ms_per_step_mixed`, `roofline_mixed_passes`), the
+host-to-host fp64 step (`ms_per_step_host_to_host`, x uploaded inside the step), `predict`, and the CPU
+baselines.
 
     --config c2 | c4 | c5      the other BASELINE configs as bench lines (same contract, their own workloads)
     --dry-run-comm             only set up the communicator, run its self-test and one all-reduce, print a JSON line
@@ -44,6 +55,11 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (guides/MI355X_MICROARCH.md); ~6300 achievable
 FP64_MFMA_PEAK_TFLOPS = 78.6   # fp64 matrix = fp64 vector rate on gfx950 (public spec)
 PREDICT_EPILOGUE_FLOPS = 14.0  # c_k of SURVEY S8(d)'s predict formula: 12 + 1 exp + 1 sqrt per kernel-matrix element
+LANDMARK_CACHE = os.path.join(ROOT, "build", "bench_cache")
+DUMP_BYTES = 60_000_000        # --dump-outputs writes at most this many bytes of array data in all
+# (cells, dims, landmarks, kernel, seed) of each BASELINE config
+CONFIG_DEFAULTS = {"c3": (1_000_000, 50, 5000, "Matern52", 3), "c2": (100_000, 20, 1000, "ExpQuad", 2),
+                   "c4": (500_000, 30, 2000, "Matern52", 4), "c5": (200_000, 50, 2000, "Matern52", 5)}
 
 
 def gaussian_mixture(n, d, seed, k=10, shard=0):
@@ -59,18 +75,35 @@ def gaussian_mixture(n, d, seed, k=10, shard=0):
     return np.ascontiguousarray(x[rng.permutation(n)])
 
 
+def _landmark_cache_file(xs, m, seed):
+    """The cache file of the sklearn route's landmarks for this subsample: a digest of its cells, m, the seed and the
+    scikit-learn version, the inputs the rounded centroids are a function of."""
+    import hashlib
+    from importlib.metadata import version
+    h = hashlib.sha256(np.ascontiguousarray(xs).tobytes())
+    h.update(f"{xs.shape} {m} {seed} scikit-learn {version('scikit-learn')}".encode())
+    return os.path.join(LANDMARK_CACHE, f"landmarks_{h.hexdigest()[:24]}.npy")
+
+
 def make_landmarks(x, m, how, ctx, seed=42, sub=100_000):
     """k-means centroids of the first <= 1e5 cells, random_state 42, computed once, untimed.
     how = "sklearn": sklearn.cluster.k_means(X[:1e5], m, n_init=1, random_state=42), the reference's own call
-    (parameters.py:291); "device": the library's k-means++ / Lloyd (mln_kmeans) on the same subsample."""
+    (parameters.py:291), kept in LANDMARK_CACHE after the first run; "device": the library's k-means++ / Lloyd
+    (mln_kmeans) on the same subsample."""
     xs = x[:min(sub, x.shape[0])]
     if m >= xs.shape[0]:
         return np.ascontiguousarray(xs[:m]), "first m cells"
     t0 = time.perf_counter()
+    cache = None
     if how == "sklearn":
+        what = f"sklearn.cluster.k_means(X[:{xs.shape[0]}], {m}, n_init=1, random_state={seed})"
+        cache = _landmark_cache_file(xs, m, seed)
+        if os.path.exists(cache):
+            c = np.load(cache)
+            if c.shape == (m, xs.shape[1]):
+                return np.ascontiguousarray(c.astype(np.float64)), f"{what}, rounded through float32, host, untimed (cached)"
         from sklearn.cluster import k_means
         c = k_means(xs, m, n_init=1, random_state=seed)[0]
-        what = f"sklearn.cluster.k_means(X[:{xs.shape[0]}], {m}, n_init=1, random_state={seed})"
     else:
         c = ctx.kmeans(xs, m, seed=seed)
         what = f"mln_kmeans (k-means++ / Lloyd on the device) on X[:{xs.shape[0]}], seed {seed}"
@@ -78,7 +111,36 @@ def make_landmarks(x, m, how, ctx, seed=42, sub=100_000):
     # centroids differ in their last bits from process to process (threaded BLAS / OpenMP reductions), enough to move
     # the L-BFGS pass count by a few evaluations; rounded through float32 they are the same numbers in every run
     c = np.ascontiguousarray(c.astype(np.float32).astype(np.float64))
+    if cache is not None:
+        try:                                    # float32 holds the rounded centroids exactly
+            os.makedirs(LANDMARK_CACHE, exist_ok=True)
+            tmp = f"{cache}.{os.getpid()}.tmp.npy"
+            np.save(tmp, c.astype(np.float32))
+            os.replace(tmp, cache)
+        except OSError as e:
+            print(f"[bench] landmark cache not written: {e}", file=sys.stderr)
     return c, f"{what}, rounded through float32, host, untimed ({dt:.1f} s)"
+
+
+def warm_landmark_cache(config="c3"):
+    """Compute and cache the sklearn landmarks of `config`'s default workload (host work, no GPU needed).  build() calls
+    it, so that the first plain run after a build does not spend a minute in k-means before its first step."""
+    n, d, m, _, seed = CONFIG_DEFAULTS[config]
+    return make_landmarks(gaussian_mixture(n, d, seed), m, "sklearn", None)[1]
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """Write each output of the last timed step as <path>/<name>.npy in float64.  An output larger than its share of
+    `budget` is replaced by a fixed sample of its rows (seed 0, in row order): the same rows in every run of the same
+    arguments, so that two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(x, landmarks, nn, kern_name, samples, n_target):
@@ -354,9 +416,20 @@ def bench_other(args, comm, ctx, info, world, rank):
                            "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                            "frac": flops / (elapsed / args.steps) / 1e12 / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
                            "note": "step-level figure (host<->device traffic of the n x p arrays included)"}
+    # ---- what the last timed step returned, all ranks' rows in order (C5: a fixed sample of the n x p predictions) -----
+    outputs = {}
+    if args.dump_outputs:
+        if args.config == "c4":
+            outputs["log_density"] = comm.allgather_rows(res)
+        else:
+            pred = res.to_host() if hasattr(res, "to_host") else np.asarray(res)
+            rows = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_BYTES // (8 * p)), replace=False))
+            mine = rows[(rows >= lo) & (rows < hi)] - lo
+            outputs["prediction_sample"] = comm.allgather_rows(pred[mine]).reshape(-1, p)
+            del pred
     # ---- CPU baseline beside it (rank 0, bounded sample of the SAME workload, the oracle = the reference's algorithm restated;
     #      kind "port"): C4 a time-sensitive density fit of an evenly spaced subsample, C5 the function fit + predict of one ------
-    if rank == 0 and args.cpu_sample != 0:
+    if rank == 0 and args.full and args.cpu_sample != 0:
         from oracle import mellon_oracle as mo
         try:
             from threadpoolctl import threadpool_limits
@@ -386,7 +459,7 @@ def bench_other(args, comm, ctx, info, world, rank):
         dt = time.perf_counter() - t0
         out["cpu_baseline"] = {"value": ns / dt, "unit": "cells/s", "cores": os.cpu_count(), "kind": "port",
                                "sample": what_cpu + f"; {dt:.1f} s wall (every stage is O(n): cells/s carries over to the full size)"}
-    return out
+    return out, outputs
 
 
 def pick_cpu_samples(args, n, host_gb):
@@ -454,7 +527,8 @@ def main():
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="strong (default): --cells in total, split N ways -- at every N the workload is BASELINE config 3 itself "
                          "(1e6 cells), which is what north_star's '>= 6x at 8 GPUs' is quoted on; weak: --cells per GPU, one model "
-                         "on N x cells.  With N > 1 the other mode's step is measured too (--extra-steps) and reported beside the headline")
+                         "on N x cells.  With N > 1 and --full the other mode's step is measured too (--extra-steps) and reported beside "
+                         "the headline")
     ap.add_argument("--dims", dest="d", type=int, default=None)
     ap.add_argument("--landmarks", dest="m", type=int, default=None)
     ap.add_argument("--landmark-method", choices=["sklearn", "device"], default="sklearn")
@@ -466,7 +540,7 @@ def main():
     ap.add_argument("--cpu-budget-s", type=float, default=330.0, help="wall-clock budget of the default CPU baseline")
     ap.add_argument("--cpu-sample-full", action="store_true",
                     help="SURVEY S8(d) sizes: 2.5e5 and 5e5 cells (needs ~60 GB of host RAM and ~15 min)")
-    ap.add_argument("--extra-steps", type=int, default=4, help="steps of the mixed-precision and host-to-host measurements")
+    ap.add_argument("--extra-steps", type=int, default=4, help="steps of the --full measurements (predict, mixed precision, host to host, N > 1 companions)")
     ap.add_argument("--pmc", action="store_true",
                     help="re-measure roofline.traffic in this run: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) of one "
                          "fp64 step, ~1 min each; without it the committed profiles/objective_traffic.json is quoted")
@@ -475,7 +549,15 @@ def main():
                          "without it a multi-rank run whose transport is not RCCL over N ranks exits non-zero")
     ap.add_argument("--dry-run-comm", action="store_true",
                     help="communicator set-up + self-test + one all-reduce of the per-evaluation size, nothing else")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the parity of predict with fit_predict, predict "
+                         "throughput, the host-to-host and mixed-precision steps, the other scaling mode and the 1-GPU step "
+                         "(N > 1), the collectives' cost, the CPU baselines.  Off: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most 60 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -534,17 +616,18 @@ def main():
                 "init_s": t_comm, "self_test": rep, "comm": comm_report}))
         return
 
-    defaults = {"c3": (1_000_000, 50, 5000, "Matern52", 3), "c2": (100_000, 20, 1000, "ExpQuad", 2),
-                "c4": (500_000, 30, 2000, "Matern52", 4), "c5": (200_000, 50, 2000, "Matern52", 5)}[args.config]
+    defaults = CONFIG_DEFAULTS[args.config]
     args.n = args.n or defaults[0]
     args.d = args.d or defaults[1]
     args.m = args.m or defaults[2]
     args.kernel = args.kernel or defaults[3]
     args.seed = defaults[4] if args.seed is None else args.seed
     if args.config in ("c4", "c5"):
-        out = bench_other(args, comm, ctx, info, world, rank)
+        out, outputs = bench_other(args, comm, ctx, info, world, rank)
         out["config"].update(comm_report)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
             _print_result_line(real_stdout, json.dumps(out))
         return
 
@@ -640,16 +723,21 @@ def main():
         del est
     elapsed, (est, dens, stats, n_eval), t_fit, t_free = timed(args.steps, x_loc_dev, keep_last=True)
 
+    # ---- what the last timed step returned, all ranks' rows in order ------------------------------------------
+    outputs = {"log_density": comm.allgather_rows(dens)} if args.dump_outputs else {}
+
     # ---- size-independent parity property at full size: predict(X) == fit_predict(X) -----------------
-    k = min(20000, hi - lo)
-    xq = x_loc[:k]
-    prop = float(np.abs(est.predict(xq) - dens[:k]).max() / np.abs(dens[:k]).max())
+    prop = None
+    if args.full:
+        k = min(20000, hi - lo)
+        xq = x_loc[:k]
+        prop = float(np.abs(est.predict(xq) - dens[:k]).max() / np.abs(dens[:k]).max())
 
     # ---- the second half of SURVEY S8(d)'s metric: n' / wall(predict).  est.predict(X) for this rank's cells (resident in HBM;
     #      the log-density lands in host memory), landmarks and weights cached by the predictor: K(X, xu) is never materialised
     #      (conditional.py:899-906, base_predictor.py:180-257).  No collective: every rank predicts its own rows. -------------
     predict_line = predict_state = pd = None
-    if args.extra_steps > 0:
+    if args.full and args.extra_steps > 0:
         predictor = est.predict
         pd = predictor(x_loc_dev)                       # builds the predictor (weights w = Lp^-T z), warms the kernel
         predict_state = (float(est.ls), np.array(predictor.weights), float(predictor.mu))
@@ -680,7 +768,7 @@ def main():
     # ---- beside the headline, same process, same inputs (untimed by the contract) -------------------------
     extra = {}
     stats_mixed = None
-    if args.extra_steps > 0:
+    if args.full and args.extra_steps > 0:
         # BASELINE.md S2's region: validated X in HOST memory -> log-density in host memory.  The caller's array is page-locked
         # once (mln_host_register, what a data loader does; untimed, like the landmarks and nn distances) so that the upload is
         # a DMA transfer under the kernel-matrix pass; the same step from pageable memory is reported beside it.
@@ -704,7 +792,7 @@ def main():
 
     # ---- the other scaling mode beside the headline (N > 1): strong headline -> the weak step (1e6 cells PER GPU, one model on
     #      N x 1e6 cells) as the companion, and the other way round -------------------------------------------------------------
-    if world > 1 and args.extra_steps > 0:
+    if args.full and world > 1 and args.extra_steps > 0:
         _, xs_dev, nn_other, n_tot2, lo2, hi2, _ = prepare(not weak)
         nn_cur[0] = nn_other
         one_step(xs_dev)[0]._fit.close()                                                 # allocator warm-up at the new sizes
@@ -722,7 +810,7 @@ def main():
 
     # ---- the 1-GPU step of the SAME run: rank 0 alone, on a private single-rank context, fits the unsharded shard-0 workload
     #      (the BASELINE config-3 problem) while the other ranks wait -- so that the N > 1 line carries its own speed-up ----------
-    if world > 1 and args.extra_steps > 0:
+    if args.full and world > 1 and args.extra_steps > 0:
         n1_ms = None
         if rank == 0:
             solo = distributed.Communicator()
@@ -754,7 +842,7 @@ def main():
                 extra["speedup_vs_n1"] = n1_ms / (1e3 * elapsed / args.steps)
 
     # ---- per-rank cost of the collectives: one more fp64 step with a pair of stream events around every collective ------
-    if world > 1:
+    if args.full and world > 1:
         ctx.comm_info(timing=True, reset=True)
         e_c, _, _, _ = timed(1, x_loc_dev)
         ci = ctx.comm_info(timing=False, reset=True)
@@ -809,7 +897,7 @@ def main():
                    "nn_distances": f"exact 1-NN on device, untimed ({t_nn:.2f} s)",
                    "timed_region": "x, landmarks, nn_distances resident (x in HBM) -> log-density in host memory; "
                                    "ms_per_step_host_to_host starts from x in host memory (BASELINE.md S2)",
-                   "predict_equals_fit_predict_rel_max": prop, "device": info["arch"], **comm_report},
+                   "device": info["arch"], **comm_report},
         "roofline": roof,
         "stages_s": {k: round(v, 4) for k, v in stats.items() if k.endswith("_s")},
         "host_s": {"fit_predict_per_step": round(t_fit / args.steps, 4), "release_per_step": round(t_free / args.steps, 4)},
@@ -825,11 +913,13 @@ def main():
             out["mfma"] = json.load(open(mfile))
         except Exception:
             pass
+    if prop is not None:
+        out["config"]["predict_equals_fit_predict_rel_max"] = prop
     if predict_line is not None:
         out["predict"] = predict_line
         if world == 1 and args.cpu_sample != 0:
             out["predict"]["cpu_baseline"] = cpu_baseline_predict(x0, landmarks, predict_state, args.kernel, pd)
-    if world == 1 and args.cpu_sample != 0:
+    if args.full and world == 1 and args.cpu_sample != 0:
         gc.collect()
         samples, why = pick_cpu_samples(args, n, host_memory_gb())
         if samples is not None:
@@ -838,6 +928,8 @@ def main():
         else:
             out["cpu_baseline"] = cpu_baseline_budgeted(x0, landmarks, nn_loc, args.kernel, n_total, args.cpu_budget_s,
                                                         host_memory_gb())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     _print_result_line(real_stdout, json.dumps(out))
 
 

@@ -23,6 +23,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # epilogue reads them directly; in AGPRs every element costs a v_accvgpr_read)
 EXTRA_FLAGS = {"rowmin_w64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
+# the persistent-row kernel families take minutes each (the product kernels the longest): they start first, and the
+# short sources fill the workers around them, instead of a slow source starting last and setting the build's wall time
+SLOW_FIRST = ("kernel_rows_prod_", "predict_rows_prod_", "cov_rows_", "predict_rows_")
+
+
+def _slow_rank(src):
+    name = os.path.basename(src)
+    return next((i for i, p in enumerate(SLOW_FIRST) if name.startswith(p)), len(SLOW_FIRST))
+
 
 def _deps(depfile, src):
     """Prerequisites recorded by -MMD (the source itself if there is no record yet)."""
@@ -59,7 +68,9 @@ def build(force=False, verbose=True):
         r = subprocess.run(cmd, capture_output=True, text=True)
         return job, r
 
-    with ThreadPoolExecutor(max_workers=min(max(8, (os.cpu_count() or 8) // 2), max(1, len(jobs)))) as ex:
+    jobs.sort(key=lambda job: _slow_rank(job[0]))
+    workers = int(os.environ.get("MAX_JOBS") or max(8, (os.cpu_count() or 8) // 2))
+    with ThreadPoolExecutor(max_workers=min(workers, max(1, len(jobs)))) as ex:
         for (src, obj, dep), r in ex.map(cc, jobs):
             if verbose and (r.stdout or r.stderr):
                 sys.stderr.write(r.stdout + r.stderr)

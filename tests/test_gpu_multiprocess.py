@@ -71,7 +71,7 @@ def test_bench_two_ranks_under_the_launcher(tmp_path, scaling):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--cells", "60000", "--dims", "10", "--landmarks", "400", "--landmark-method", "device", "--cpu-sample", "0",
-           "--extra-steps", "1"] + (["--scaling", scaling] if scaling else [])
+           "--extra-steps", "1", "--full"] + (["--scaling", scaling] if scaling else [])
     run = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-4000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]

@@ -205,6 +205,38 @@ def test_bench_prints_exactly_one_stdout_line():
     assert "buffered C noise" in out.stderr and "late C noise" in out.stderr
 
 
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float64 files; an output within its share of the budget whole, a larger one as the same
+    sample of its rows (seed 0, in row order) in every run."""
+    import bench
+    small = np.arange(10.0)
+    big = np.random.default_rng(1).normal(size=(5000, 40)).astype(np.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"small": small, "big": big}, budget=400_000)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (625, 40) and np.array_equal(a, b)
+    idx = np.sort(np.random.default_rng(0).choice(5000, 625, replace=False))
+    assert np.array_equal(a, big[idx].astype(np.float64))
+
+
+def test_bench_landmark_cache(tmp_path, monkeypatch):
+    """The sklearn landmarks come from the cache on the second call, the same numbers; other cells, another entry."""
+    import bench
+    from sklearn.cluster import k_means
+    monkeypatch.setattr(bench, "LANDMARK_CACHE", str(tmp_path / "cache"))
+    x = bench.gaussian_mixture(3000, 6, 11)
+    c1, note1 = bench.make_landmarks(x, 40, "sklearn", None)
+    assert len(os.listdir(tmp_path / "cache")) == 1 and "cached" not in note1
+    c2, note2 = bench.make_landmarks(x, 40, "sklearn", None)
+    assert "cached" in note2 and c2.dtype == np.float64 and np.array_equal(c1, c2)
+    ref = k_means(x, 40, n_init=1, random_state=42)[0]
+    assert np.abs(c1 - ref).max() < 1e-5 * np.abs(ref).max()
+    _, note3 = bench.make_landmarks(bench.gaussian_mixture(3000, 6, 12), 40, "sklearn", None)
+    assert "cached" not in note3 and len(os.listdir(tmp_path / "cache")) == 2
+
+
 def test_normalize_per_time_point_validation_and_target_counts():
     """parameter_validation.py:266-280 and parameters.py:436-441 of the reference: dict -> by time value,
     list / array -> by position among the sorted time points, True -> the average count."""

@@ -5,9 +5,9 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06; mkdir -p $O
 COMMIT=$1 bash tools/profile_round.sh r06 > $O/profile_round.log 2>&1 < /dev/null
-timeout 900 python bench.py > $O/r06_bench_c3_1gpu.json 2> $O/bench_c3.err < /dev/null
+timeout 900 python bench.py --full > $O/r06_bench_c3_1gpu.json 2> $O/bench_c3.err < /dev/null
 for c in c2 c4 c5; do
-  timeout 600 python bench.py --config $c > $O/r06_bench_$c.json 2> $O/bench_$c.err < /dev/null
+  timeout 600 python bench.py --config $c --full > $O/r06_bench_$c.json 2> $O/bench_$c.err < /dev/null
   bash tools/r06_cfg_trace.sh $c > $O/cfg_$c.log 2>&1 < /dev/null
 done
 timeout 600 python tools/emulate_rank.py 1 2 4 8 > $O/r06_emulated_ranks.json 2> $O/emu.err < /dev/null
