@@ -154,6 +154,18 @@ int mln_kernel_gram(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, i
                     const double* xu, int64_t m, double* out /* m x m */);
 int mln_nn_distances(mln_ctx* ctx, const double* x, int64_t n, const double* y, int64_t m, int32_t d,
                      int64_t self_offset, double* out /* n */);
+/* Exact k nearest neighbours (dimensionality_estimator.py:377-394 via parameters.py:352-405, util.py:486-536): for each
+ * row of x (n x d) the k rows of y (m x d) nearest in Euclidean distance, ascending, ties broken by the smaller index;
+ * with exclude != 0 the pair (i, i + self_offset) is skipped (as in mln_nn_distances).  1 <= k <= 64, k <= m (k <= m - 1
+ * with exclude), any d.  dist: n x k, sqrt(sum (x - y)^2) in fp64 (difference form: close neighbours keep their digits);
+ * idx: n x k (may be NULL).  O(n k) working memory (csrc/dimensionality.hip). */
+int mln_knn(mln_ctx* ctx, const double* x, int64_t n, const double* y, int64_t m, int32_t d, int32_t k,
+            int32_t exclude, int64_t self_offset, double* dist /* n x k */, int64_t* idx /* n x k or NULL */);
+/* Local fractal dimension (util.py:486-536): for query i, the k rows x[nbr[i, :]] (2 <= k <= 64), their k(k-1)/2 pair
+ * distances sorted ascending, and the least-squares slope of log(1 .. k(k-1)/2) on [log(distance), 1] in closed form.
+ * A zero pair distance gives NaN for that query (as lstsq on log 0). x: n x d, nbr: q x k (host or device). */
+int mln_local_dimensionality(mln_ctx* ctx, const double* x, int64_t n, int32_t d, const int64_t* nbr, int64_t q,
+                             int32_t k, double* out /* q */);
 
 /* k-means landmarks (S8f rank 1): k-means++ seeding + Lloyd sweeps on the device, the algorithm
  * family of sklearn.cluster.k_means(x, m, n_init=1, random_state) that parameters.compute_landmarks
@@ -333,6 +345,20 @@ typedef struct {
 int mln_map_solve(mln_fit* fit, const double* z0, const mln_solver_opts* opts /* NULL = defaults */,
                   double* z_out /* m */, double* loss_out, int32_t* n_eval_out, int32_t* n_iter_out,
                   int32_t* status_out);
+
+/* DimensionalityEstimator likelihood (inference.py:95-122,142-164,195-219): with the k-NN distances r_ij of this shard,
+ *   ell = log(sort(r)_ij) + log(pi) / 2   (n_local x k, 1 <= k <= 64, computed by the caller),
+ *   dims = exp(mu_dim + L z[0]),  log_dens = mu_dens + L z[1],
+ *   pred_ij = log_dens_i + dims_i ell_ij - lnGamma(dims_i / 2 + 1),
+ *   loss(z) = 1/2 |z|^2 + log 2 pi - sum_ij [pred_ij j - exp(pred_ij) - lnGamma(j)]
+ * (the prior's constant is the reference's (K/2) log 2 pi with K = 2 latent functions, dimensionality_estimator.py:389-394).
+ * z, grad, hess_diag: 2 x m, row 0 the log-dimensionality, row 1 the log-density.  One pass over the n x m buffer per
+ * evaluation computes both L z[0] and L z[1] and both back-projections; the Hessian diagonal (explicit L only, like
+ * mln_objective) takes a second pass.  One pass covers m <= 5120 landmarks; beyond, MLN_ERR_UNSUPPORTED.  A non-finite
+ * loss is returned as +inf.  Sums are all-reduced over ranks; prior terms are added once. */
+int mln_fit_set_dim_likelihood(mln_fit* fit, const double* ell, int32_t k, double mu_dim, double mu_dens);
+int mln_dim_objective(mln_fit* fit, const double* z, double* loss, double* grad /* 2 x m */,
+                      double* hess_diag /* 2 x m or NULL */);
 
 /* a-11: f = L z + mu on this shard (inference.py:51-69,341-354).                                */
 int mln_transform(mln_fit* fit, const double* z, double mu, double* f_out /* n_local */);

@@ -13,6 +13,7 @@ from .util import GaussianProcessType  # noqa: F401
 
 _LAZY = {
     "DensityEstimator": ".density_estimator",
+    "DimensionalityEstimator": ".dimensionality_estimator",
     "FunctionEstimator": ".function_estimator",
     "TimeSensitiveDensityEstimator": ".time_sensitive_density_estimator",
     "Predictor": ".base_predictor",

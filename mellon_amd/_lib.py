@@ -78,6 +78,8 @@ SYMBOLS = [
     ("mln_predict_hessian", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp]),
     ("mln_kernel_gram", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp]),
     ("mln_nn_distances", C.c_int, [_vp, _dp, _i64, _dp, _i64, _i32, _i64, _dp]),
+    ("mln_knn", C.c_int, [_vp, _dp, _i64, _dp, _i64, _i32, _i32, _i32, _i64, _dp, _vp]),
+    ("mln_local_dimensionality", C.c_int, [_vp, _dp, _i64, _i32, _vp, _i64, _i32, _dp]),
     ("mln_kmeans", C.c_int, [_vp, _dp, _i64, _i32, _i64, _i64, _i32, _dbl, _dp, C.POINTER(_i32), C.POINTER(_dbl)]),
     ("mln_kmeans_sklearn", C.c_int, [_vp, _dp, _i64, _i32, _i64, _i64, _dp, _i32, _i32, _dbl, _dp, _vp, C.POINTER(_i32),
                                      C.POINTER(_dbl)]),
@@ -107,6 +109,8 @@ SYMBOLS = [
                                 C.POINTER(_i32), C.POINTER(_i32)]),
     ("mln_fit_set_likelihood", C.c_int, [_vp, _dp, _dp, _dbl]),
     ("mln_objective", C.c_int, [_vp, _dp, C.POINTER(_dbl), _dp, _dp]),
+    ("mln_fit_set_dim_likelihood", C.c_int, [_vp, _dp, _i32, _dbl, _dbl]),
+    ("mln_dim_objective", C.c_int, [_vp, _dp, C.POINTER(_dbl), _dp, _dp]),
     ("mln_transform", C.c_int, [_vp, _dp, _dbl, _dp]),
     ("mln_weights_cholesky", C.c_int, [_vp, _dp, _dp]),
     ("mln_weights_full", C.c_int, [_vp, _dp, _i64, _dbl, _dp]),
@@ -425,6 +429,44 @@ class Context:
         out = np.empty(x.shape[0], dtype=np.float64)
         self._check(self.lib.mln_nn_distances(self.handle, _ptr(x), x.shape[0], _ptr(y), y.shape[0], x.shape[1],
                                               int(self_offset), out.ctypes.data))
+        return out
+
+    KNN_MAX_K = 64
+
+    def knn(self, x, k, y=None, exclude_self=False, self_offset=0, return_index=True):
+        """The k rows of y (default: x itself) nearest to each row of x, ascending: (dist n x k, idx n x k int64).
+        exclude_self skips the pair (i, i + self_offset).  Exact; ties go to the smaller index."""
+        x = x if isinstance(x, DeviceArray) else _as2d(x)
+        y = x if y is None else (y if isinstance(y, DeviceArray) else _as2d(y))
+        k = int(k)
+        avail = y.shape[0] - (1 if exclude_self else 0)
+        if not 1 <= k <= self.KNN_MAX_K or k > avail:
+            raise ValueError(f"k={k} is outside [1, min({self.KNN_MAX_K}, {avail})] for {y.shape[0]} candidate rows")
+        if x.shape[1] != y.shape[1]:
+            raise ValueError(f"x has {x.shape[1]} features, y has {y.shape[1]}")
+        n = x.shape[0]
+        dist = np.empty((n, k), dtype=np.float64)
+        idx = np.empty((n, k), dtype=np.int64) if return_index else None
+        self._check(self.lib.mln_knn(self.handle, _ptr(x), n, _ptr(y), y.shape[0], x.shape[1], k, int(bool(exclude_self)),
+                                     int(self_offset), dist.ctypes.data, None if idx is None else idx.ctypes.data))
+        return (dist, idx) if return_index else dist
+
+    def local_dimensionality(self, x, neighbor_idx):
+        """Per query, the least-squares slope of log(1..kc2) on the sorted log pair distances of its neighbourhood
+        x[neighbor_idx[i]] (util.py:486-536)."""
+        x = x if isinstance(x, DeviceArray) else _as2d(x)
+        nbr = np.ascontiguousarray(neighbor_idx, dtype=np.int64)
+        if nbr.ndim != 2:
+            raise ValueError(f"neighbor_idx must be 2-d, got shape {nbr.shape}")
+        q, k = nbr.shape
+        if not 2 <= k <= self.KNN_MAX_K:
+            raise ValueError(f"neighbourhoods of {k} rows: the local dimension needs 2 ... {self.KNN_MAX_K}")
+        if nbr.size and (nbr.min() < -x.shape[0] or nbr.max() >= x.shape[0]):
+            raise IndexError(f"neighbor_idx outside [0, {x.shape[0]})")
+        nbr = np.where(nbr < 0, nbr + x.shape[0], nbr)
+        out = np.empty(q, dtype=np.float64)
+        self._check(self.lib.mln_local_dimensionality(self.handle, _ptr(x), x.shape[0], x.shape[1], nbr.ctypes.data, q, k,
+                                                      out.ctypes.data))
         return out
 
     def kmeans(self, x, m, seed=42, max_iter=300, tol=1e-4, return_info=False, init="device"):
@@ -1021,6 +1063,25 @@ class Fit:
         hess = np.empty(self.m, dtype=np.float64) if with_hess else None
         self._check(self.lib.mln_objective(self.handle, z.ctypes.data, C.byref(loss), grad.ctypes.data,
                                                _ptr(hess)))
+        return (loss.value, grad, hess) if with_hess else (loss.value, grad)
+
+    def set_dim_likelihood(self, ell, mu_dim, mu_dens):
+        """ell: n x k, log of the sorted k-NN distances + log(pi) / 2 (mln_fit_set_dim_likelihood)."""
+        ell = _f64(ell)
+        if ell.ndim != 2 or ell.shape[0] != self.n:
+            raise ValueError(f"ell has shape {ell.shape}, expected ({self.n}, k)")
+        self._check(self.lib.mln_fit_set_dim_likelihood(self.handle, ell.ctypes.data, int(ell.shape[1]), float(mu_dim),
+                                                        float(mu_dens)))
+
+    def dim_objective(self, z, with_hess=False):
+        """(loss, grad[, hess_diag]) of the dimensionality objective at z (2 x m)."""
+        z = _f64(z)
+        if z.shape != (2, self.m):
+            raise ValueError(f"z has shape {z.shape}, expected {(2, self.m)}")
+        loss = C.c_double()
+        grad = np.empty((2, self.m), dtype=np.float64)
+        hess = np.empty((2, self.m), dtype=np.float64) if with_hess else None
+        self._check(self.lib.mln_dim_objective(self.handle, z.ctypes.data, C.byref(loss), grad.ctypes.data, _ptr(hess)))
         return (loss.value, grad, hess) if with_hess else (loss.value, grad)
 
     def precond_build(self, row_stride=1, row_offset=0, force=False):

@@ -21,7 +21,8 @@ void fit_free(mln_fit* f) {
   triinv_free(&f->tri);
   void* ptrs[] = {f->V, f->Vdr, f->part_grad, f->part_hess, f->part_loss, f->d_z, f->d_out,
                   f->C, f->Cinv, f->d_u, f->d_gu, f->d_tmp, f->P, f->d_w, f->d_w_cached,
-                  f->Q1, f->Q2, f->d_zw, f->d_zr, f->eigU, f->L32, f->sv_block, f->f_keep[0], f->f_keep[1], f->Kj, f->d_over};
+                  f->Q1, f->Q2, f->d_zw, f->d_zr, f->eigU, f->L32, f->sv_block, f->f_keep[0], f->f_keep[1], f->Kj, f->d_over,
+                  f->dim_ell, f->dim_part, f->dim_z, f->dim_out};
   for (void* p : ptrs) if (p) (void)mln_dfree(p);
   for (double* p : f->saved_precond) if (p) (void)mln_dfree(p);
   if (f->h_state) (void)mln_hfree(f->h_state);

@@ -162,6 +162,12 @@ struct mln_fit {
   double build_seconds = 0.0;     // wall time of the first preconditioner build (Gram + factorisation): the rebuild's price
   double times_sub = 0.0, times_rebuild = 0.0, sub_pass_equiv = 0.0;
   int evals_sub = 0, n_rebuild = 0;
+  // dimensionality likelihood (dimensionality.hip): ell = log(sorted k-NN distance) + log(pi) / 2 (n x dim_k), the two means,
+  // the partials of one pass (n_wg x 4 ldl: both gradients, both Hessian diagonals), z and w (4 ldl), the reduced sums
+  double* dim_ell = nullptr;
+  int dim_k = 0;
+  double mu_dim = 0.0, mu_dens = 0.0;
+  double *dim_part = nullptr, *dim_z = nullptr, *dim_out = nullptr;
 };
 
 // device scratch that frees itself (after draining the stream) on every exit path

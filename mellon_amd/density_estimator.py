@@ -8,7 +8,7 @@ import numpy as np
 from .base_model import BaseEstimator, DEFAULT_COV_FUNC
 from .inference import (DEFAULT_INIT_LEARN_RATE, DEFAULT_JIT, DEFAULT_N_ITER, DEFAULT_OPTIMIZER,
                         compute_conditional, compute_log_density_x, compute_loss_func, compute_transform)
-from .parameters import DEFAULT_RANDOM_SEED, compute_d, compute_initial_value, compute_mu
+from .parameters import DEFAULT_RANDOM_SEED, compute_d, compute_d_factal, compute_initial_value, compute_mu
 from .util import DEFAULT_JITTER
 from .validation import validate_array, validate_float_or_iterable_numerical, validate_string
 
@@ -71,8 +71,11 @@ class DensityEstimator(BaseEstimator):
     # -- attribute computations (reference density_estimator.py:311-402) --------------------------------
     def _compute_d(self):
         if self.d_method == "fractal":
-            raise NotImplementedError("d_method='fractal' (util.local_dimensionality) is outside the accelerated path.")
-        d = self.d if self.d_method == "manual" else compute_d(self.x)
+            # parameters.compute_d_factal: the mean local dimension of 500 cells (NumPy's draw, not JAX's: see there)
+            self._require_single_process("d")
+            d = compute_d_factal(self.x)
+        else:
+            d = self.d if self.d_method == "manual" else compute_d(self.x)
         logger.info(f"Using d={d}.")
         if np.ndim(d) == 0 and d > 50:
             raise ValueError(

@@ -1,0 +1,217 @@
+"""DimensionalityEstimator (mellon/dimensionality_estimator.py): same constructor, attributes and
+prepare_inference / run_inference / process_inference / fit / fit_predict flow, `predict` (local dimensionality) and
+`predict_density`.  The k-NN search, the local fractal dimension, the covariance factorisation and the MAP objective of
+the (log-dimensionality, log-density) pair run on the MI355X; SciPy's L-BFGS-B drives the objective from the host.
+
+Deliberate deviation: duplicate cells give a zero nearest-neighbour distance and log 0 in the likelihood; the reference's
+solve then sees an infinite loss and stops where it started.  This estimator raises a ValueError naming the count of
+zero distances (or of non-finite local dimensions) before the solve instead."""
+import logging
+
+import numpy as np
+
+from .base_model import BaseEstimator, DEFAULT_COV_FUNC
+from .inference import (DEFAULT_INIT_LEARN_RATE, DEFAULT_JIT, DEFAULT_N_ITER, DEFAULT_OPTIMIZER,
+                        compute_conditional, compute_conditional_explog, compute_dimensionality_loss_func,
+                        compute_dimensionality_transform, compute_log_density_x)
+from .parameters import DEFAULT_RANDOM_SEED, compute_initial_dimensionalities, compute_mu
+from .util import DEFAULT_JITTER, ensure_2d
+from .validation import validate_array, validate_float, validate_k, validate_positive_int
+
+logger = logging.getLogger("mellon")
+
+LOCAL_DIM_K = 30      # neighbours of the local fractal dimension (util.local_dimensionality's default)
+
+
+class DimensionalityEstimator(BaseEstimator):
+    """Local intrinsic dimensionality and density (reference dimensionality_estimator.py:35-677)."""
+
+    def __init__(self, cov_func_curry=DEFAULT_COV_FUNC, n_landmarks=None, rank=None, gp_type=None,
+                 jitter=DEFAULT_JITTER, optimizer=DEFAULT_OPTIMIZER, n_iter=DEFAULT_N_ITER,
+                 init_learn_rate=DEFAULT_INIT_LEARN_RATE, landmarks=None, k=10, distances=None, d=None, mu_dim=0,
+                 mu_dens=None, ls=None, ls_factor=1, cov_func=None, Lp=None, L=None, initial_value=None,
+                 predictor_with_uncertainty=False, jit=DEFAULT_JIT, check_rank=None,
+                 random_state=DEFAULT_RANDOM_SEED):
+        super().__init__(cov_func_curry=cov_func_curry, n_landmarks=n_landmarks, rank=rank, gp_type=gp_type,
+                         jitter=jitter, optimizer=optimizer, n_iter=n_iter, init_learn_rate=init_learn_rate,
+                         landmarks=landmarks, nn_distances=None, d=d, mu=mu_dens, ls=ls, ls_factor=ls_factor,
+                         cov_func=cov_func, Lp=Lp, L=L, initial_value=initial_value,
+                         predictor_with_uncertainty=predictor_with_uncertainty, jit=jit, check_rank=check_rank,
+                         random_state=random_state)
+        self.k = validate_positive_int(k, "k")
+        self.mu_dim = validate_float(mu_dim, "mu_dim")
+        self.mu_dens = validate_float(mu_dens, "mu_dens", optional=True)
+        self.distances = validate_array(distances, "distances", optional=True)
+        self.transform = None
+        self.loss_func = None
+        self.opt_state = None
+        self.losses = None
+        self.pre_transformation = None
+        self.pre_transformation_std = None
+        self.local_dim_x = None
+        self.log_density_x = None
+        self.local_dim_func = None
+        self.log_density_func = None
+
+    def __repr__(self):
+        def s(v):
+            if v is None:
+                return "None"
+            return f"<array {tuple(v.shape)}>" if hasattr(v, "shape") else str(v)
+        keys = ("n_landmarks", "rank", "gp_type", "jitter", "k", "d", "mu_dim", "mu_dens", "ls", "cov_func",
+                "landmarks", "Lp", "L", "distances", "initial_value", "optimizer")
+        return self.__class__.__name__ + "(" + ", ".join(f"{k}={s(getattr(self, k, None))}" for k in keys) + ")"
+
+    # -- attribute computations (reference dimensionality_estimator.py:345-467) --------------------------------
+    def _compute_distances(self):
+        """The k nearest other cells (dimensionality_estimator.py:375-384), from ONE exact device search with
+        max(k + 1, 30) neighbours that also gives the local dimension its neighbourhoods: column 0 is the cell itself
+        (or a coincident cell, at distance 0), columns 1 .. k are the distances."""
+        logger.info("Computing distances.")
+        from . import _lib
+        x = self._host_x()
+        n = x.shape[0]
+        validate_k(self.k, n)
+        kk = max(self.k + 1, min(LOCAL_DIM_K, n))
+        dist, idx = _lib.default_context().knn(x, kk, return_index=True)
+        self._knn_idx = (self.x, idx[:, :min(LOCAL_DIM_K, n)])
+        return np.ascontiguousarray(dist[:, 1:self.k + 1])
+
+    def _compute_nn_distances(self):
+        nn = np.ascontiguousarray(np.asarray(self.distances, dtype=np.float64)[:, 0])
+        zeros = int(np.count_nonzero(nn <= 0))
+        if zeros:
+            raise ValueError(f"{zeros} cells have a nearest-neighbour distance of 0 (duplicate cells): the likelihood "
+                             "takes its logarithm. Remove or jitter the duplicates.")
+        return nn
+
+    def _compute_d(self):
+        from .util import local_dimensionality
+        held = self.__dict__.pop("_knn_idx", None)
+        x = self._host_x()
+        if held is not None and held[0] is self.x:
+            d = local_dimensionality(x, k=held[1].shape[1], neighbor_idx=held[1])
+        else:
+            d = local_dimensionality(x)
+        bad = int(np.count_nonzero(~np.isfinite(d)))
+        if bad:
+            raise ValueError(f"{bad} cells have a non-finite local dimension (a zero distance among their "
+                             f"{LOCAL_DIM_K} nearest neighbours: duplicate cells). Remove or jitter the duplicates.")
+        return d
+
+    def _compute_mu_dens(self):
+        return compute_mu(self.nn_distances, self.d)
+
+    def _compute_initial_value(self):
+        return compute_initial_dimensionalities(self.x, self.mu_dim, self.mu_dens, self.L, self.nn_distances, self.d)
+
+    def _compute_transform(self):
+        return compute_dimensionality_transform(self.mu_dim, self.mu_dens, self.L)
+
+    def _compute_loss_func(self):
+        return compute_dimensionality_loss_func(self.distances, self.transform, self.initial_value.shape[0])
+
+    def _host_x(self):
+        from . import _lib
+        x = self.x.to_host() if isinstance(self.x, _lib.DeviceArray) else self.x
+        return np.ascontiguousarray(ensure_2d(np.asarray(x, dtype=np.float64)))
+
+    def _set_local_dim_x(self):
+        self.local_dim_x, self.log_density_x = compute_log_density_x(self.pre_transformation, self.transform)
+
+    def _row(self, a, i):
+        return None if a is None else np.asarray(a).reshape(2, -1)[i, :]
+
+    def _set_local_dim_func(self):
+        logger.info("Computing predictive dimensionality function.")
+        self.local_dim_func = compute_conditional_explog(
+            self.x, self.landmarks, self._row(self.pre_transformation, 0), self._row(self.pre_transformation_std, 0),
+            self.local_dim_x, self.mu_dim, self.cov_func, self.L, self.Lp, sigma=None, jitter=self.jitter,
+            y_is_mean=True, with_uncertainty=self.predictor_with_uncertainty)
+
+    def _set_log_density_func(self):
+        logger.info("Computing predictive density function.")
+        self.log_density_func = compute_conditional(
+            self.x, self.landmarks, self._row(self.pre_transformation, 1), self._row(self.pre_transformation_std, 1),
+            self.log_density_x, self.mu_dens, self.cov_func, self.L, self.Lp, sigma=None, jitter=self.jitter,
+            y_is_mean=True, with_uncertainty=self.predictor_with_uncertainty)
+
+    # -- public flow (reference dimensionality_estimator.py:469-677) -----------------------------------------------
+    _PIPELINE = ("n_landmarks", "rank", "gp_type", None, "distances", "nn_distances", "d", "mu_dens", "ls", "cov_func",
+                 "landmarks", "Lp", "L", "initial_value", "transform", "loss_func")
+
+    def prepare_inference(self, x):
+        if x is None:
+            if self.x is None:
+                raise ValueError("Required argument x is missing and self.x has not been set.")
+            x = self.x
+        elif self.x is not None and self.x is not x:
+            raise ValueError("self.x has been set already, but is not equal to the argument x.")
+        from .distributed import current
+        if current().world_size > 1:
+            raise NotImplementedError("DimensionalityEstimator does not support cells sharded over several ranks: "
+                                      "fit it in a single process with all cells.")
+        self.set_x(x)
+        from .util import log_nn_new_fit
+        log_nn_new_fit()
+        try:
+            for attr in self._PIPELINE:
+                if attr is None:
+                    self.validate_parameter()
+                else:
+                    self._prepare_attribute(attr)
+        finally:
+            self._release_x_on_device()
+        return self.loss_func, self.initial_value
+
+    def run_inference(self, loss_func=None, initial_value=None, optimizer=None):
+        if loss_func is not None:
+            self.loss_func = loss_func
+        if initial_value is not None:
+            self.initial_value = initial_value
+        if optimizer is not None:
+            self.optimizer = optimizer
+        self._run_inference()
+        self.pre_transformation = np.asarray(self.pre_transformation).reshape(2, -1)
+        if self.pre_transformation_std is not None:
+            self.pre_transformation_std = np.asarray(self.pre_transformation_std).reshape(2, -1)
+        return self.pre_transformation
+
+    def process_inference(self, pre_transformation=None, build_predict=True):
+        if pre_transformation is not None:
+            self.pre_transformation = validate_array(pre_transformation, "pre_transformation")
+        self._set_local_dim_x()
+        if build_predict:
+            self._set_local_dim_func()
+            self._set_log_density_func()
+        return self.local_dim_x, self.log_density_x
+
+    def fit(self, x=None, build_predict=True):
+        self.prepare_inference(x)
+        self.run_inference()
+        self.process_inference(build_predict=build_predict)
+        return self
+
+    @property
+    def predict_density(self):
+        if self.log_density_func is None:
+            self._set_log_density_func()
+        return self.log_density_func
+
+    @property
+    def predict(self):
+        if self.local_dim_func is None:
+            self._set_local_dim_func()
+        return self.local_dim_func
+
+    def fit_predict(self, x=None, build_predict=False):
+        if self.x is not None and x is not None and self.x is not x:
+            raise ValueError("self.x has been set already, but is not equal to the argument x.")
+        if self.x is None and x is None:
+            raise ValueError("Required argument x is missing and self.x has not been set.")
+        if x is None:
+            x = self.x
+        else:
+            x = validate_array(x, "x")
+        self.fit(x, build_predict=build_predict)
+        return self.local_dim_x

@@ -123,6 +123,83 @@ def compute_loss_func(nn_distances, d, transform, k, constants=None):
     return LossFunc(nn_distances, d, transform, k, constants)
 
 
+class DimensionalityTransform:
+    """z (2 x m) -> (exp(mu_dim + L z[0]), mu_dens + L z[1]) (inference.py:142-164): two passes over the same factor."""
+
+    def __init__(self, mu_dim, mu_dens, L):
+        self.mu_dim, self.mu_dens = float(mu_dim), float(mu_dens)
+        self.L = L
+        self.fit = _fit_of(L)
+
+    def __call__(self, z):
+        z = np.asarray(z, dtype=np.float64).reshape(2, -1)
+        return np.exp(self.fit.transform(z[0], self.mu_dim)), self.fit.transform(z[1], self.mu_dens)
+
+
+def compute_dimensionality_transform(mu_dim, mu_dens, L):
+    return DimensionalityTransform(mu_dim, mu_dens, L)
+
+
+class DimensionalityLossFunc:
+    """loss(z) = -(prior(z) + Poisson likelihood of the k-NN distances) (inference.py:95-122,195-219), z of shape (2, m):
+    row 0 the log-dimensionality, row 1 the log-density.  One device pass over L per evaluation computes the loss and both
+    gradient rows (mln_dim_objective).  The prior's constant counts k = initial_value.shape[0] = 2 latent functions, as
+    the reference's does.  Flat vectors (SciPy's) are accepted and returned flat.
+    The objective is not convex in the log-dimensionality: the preconditioned variable (the Ridge factor of the handle,
+    applied to each row) only changes the conditioning, and the solve stays SciPy's L-BFGS-B from the Ridge start."""
+
+    def __init__(self, distances, transform, k):
+        self.fit = transform.fit
+        self.k = int(k)
+        r = np.asarray(distances, dtype=np.float64)
+        if r.ndim != 2 or r.shape[0] != self.fit.n:
+            raise ValueError(f"distances of shape {r.shape} for {self.fit.n} rows of L")
+        with np.errstate(divide="ignore"):
+            ell = np.log(np.sort(r, axis=-1)) + np.log(np.pi) / 2
+        self.fit.set_dim_likelihood(ell, transform.mu_dim, transform.mu_dens)
+        self.n_eval = 0
+        self.preconditioned = True
+        self.native_solver = False     # the in-library L-BFGS serves the density objective only
+
+    def _split(self, z):
+        return np.asarray(z, dtype=np.float64).reshape(2, self.fit.m)
+
+    def value_and_grad(self, z):
+        self.n_eval += 1
+        loss, grad = self.fit.dim_objective(self._split(z))
+        return loss, grad.reshape(np.shape(z))
+
+    def value_and_grad_u(self, u):
+        self.n_eval += 1
+        uu = self._split(u)
+        z = np.stack([self.fit.precond_apply(1, uu[0]), self.fit.precond_apply(1, uu[1])])
+        loss, g = self.fit.dim_objective(z)
+        gu = np.stack([self.fit.precond_apply(2, g[0]), self.fit.precond_apply(2, g[1])])
+        return loss, gu.reshape(np.shape(u))
+
+    def u_from_z(self, z):
+        """Flat, for SciPy."""
+        zz = self._split(z)
+        return np.concatenate([self.fit.precond_apply(0, zz[0]), self.fit.precond_apply(0, zz[1])])
+
+    def z_from_u(self, u):
+        uu = self._split(u)
+        return np.stack([self.fit.precond_apply(1, uu[0]), self.fit.precond_apply(1, uu[1])])
+
+    def hessian_diagonal(self, z):
+        if getattr(self.fit, "implicit", False):
+            raise NotImplementedError("the Hessian diagonal needs the explicit factor L "
+                                      "(fit prepared with implicit=False; predictor_with_uncertainty does this)")
+        return self.fit.dim_objective(self._split(z), with_hess=True)[2]
+
+    def __call__(self, z):
+        return self.value_and_grad(z)[0]
+
+
+def compute_dimensionality_loss_func(distances, transform, k):
+    return DimensionalityLossFunc(distances, transform, k)
+
+
 def minimize_lbfgsb(loss_func, initial_value, jit=DEFAULT_JIT, options=None):
     """inference.py:272-288.  `options` overrides LBFGSB_OPTIONS.  options="reference" runs the reference AS RUN:
     SciPy's L-BFGS-B (the routine behind jaxopt.ScipyMinimize) with its default stopping rule (ftol 2.2e-9, gtol 1e-5,
@@ -165,8 +242,8 @@ def minimize_lbfgsb(loss_func, initial_value, jit=DEFAULT_JIT, options=None):
         fun, jac = loss_func.value_and_grad, True
     else:
         fun, jac = loss_func, None                       # user callable: finite differences by SciPy
-    res = _sp_minimize(fun, z0, jac=jac, method="L-BFGS-B", options=opts)
-    return Results(res.x, res, float(res.fun))
+    res = _sp_minimize(fun, z0.ravel(), jac=jac, method="L-BFGS-B", options=opts)
+    return Results(res.x.reshape(z0.shape), res, float(res.fun))      # (SciPy works on a flat vector)
 
 
 def _unavailable_optimizer(name):
@@ -264,7 +341,12 @@ def compute_conditional_times(x, landmarks, pre_transformation, pre_transformati
 def compute_conditional_explog(x, landmarks, pre_transformation, pre_transformation_std, y, mu, cov_func, L,
                                Lp=None, sigma=0, jitter=DEFAULT_JITTER, y_is_mean=False, with_uncertainty=False,
                                obs_variance=False):
-    """inference.py:643-765 (exp of the predicted log value)."""
+    """inference.py:643-765 (exp of the predicted log value).  The full and landmarks branches condition on log(y)
+    (inference.py:707,753); the landmarks-Cholesky branch conditions on the latent pre_transformation and never reads y."""
+    cholesky = landmarks is not None and pre_transformation is not None and \
+        np.shape(pre_transformation)[0] == ensure_2d(landmarks).shape[0]
+    if not cholesky and y is not None:
+        y = np.log(np.asarray(y, dtype=np.float64))
     return _dispatch((ExpFullConditional, ExpLandmarksConditional, ExpLandmarksConditionalCholesky), x, landmarks,
                      pre_transformation, pre_transformation_std, y, mu, cov_func, L, Lp, sigma, jitter, y_is_mean,
                      with_uncertainty, obs_variance)

@@ -131,17 +131,18 @@ def compute_landmarks_rescale_time(x, ls, ls_time, times=None, n_landmarks=DEFAU
 
 
 def compute_distances(x, k, seed=DEFAULT_RANDOM_SEED):
-    """Distances to the k nearest neighbours.  The reference uses pynndescent (approximate,
-    parameters.py:352-405); this is the exact Euclidean answer from a space-partitioning tree."""
+    """Distances to the k nearest neighbours, self excluded (n x k, ascending).  The reference uses pynndescent
+    (approximate, parameters.py:352-405); this is the exact Euclidean answer of the device search (mln_knn, k <= 64);
+    `seed` only matters for the reference's search."""
+    if isinstance(x, _lib.DeviceArray):
+        x = x.to_host()
     x = ensure_2d(validate_array(x, "x"))
     n = x.shape[0]
     if n == 0:
         raise ValueError("Input data x is empty.")
     validate_k(k, n)
-    from sklearn.neighbors import BallTree, KDTree
-    tree = (KDTree if x.shape[1] <= 20 else BallTree)(x)
-    dist, _ = tree.query(x, k=k + 1)
-    return dist[:, 1:]
+    return _lib.default_context().knn(np.ascontiguousarray(x, dtype=np.float64), k, exclude_self=True,
+                                      return_index=False)
 
 
 def compute_nn_distances(x, seed=DEFAULT_RANDOM_SEED):
@@ -222,6 +223,28 @@ def compute_d(x):
     """reference parameters.py:534-549: the embedding dimensionality."""
     x = np.asarray(x) if not isinstance(x, _lib.DeviceArray) else x
     return 1 if len(x.shape) < 2 else x.shape[1]
+
+
+FRACTAL_DRAW = "numpy.random.default_rng(seed).choice(n_cells, size=n, replace=False)"
+
+
+def compute_d_factal(x, k=10, n=500, seed=432):
+    """reference parameters.py:545-583: the mean local fractal dimension (util.local_dimensionality with k neighbours)
+    over n cells drawn without replacement, or over all cells when there are at most n.  The reference draws the cells
+    with JAX's random.choice(PRNGKey(seed), ...); this mirror draws them with NumPy's generator seeded the same way
+    (FRACTAL_DRAW), so the cells -- and the mean -- differ from the reference's at more than n cells."""
+    from .util import local_dimensionality
+    if isinstance(x, _lib.DeviceArray):
+        x = x.to_host()
+    x = np.asarray(x)
+    if x.ndim < 2:
+        return 1
+    if n < x.shape[0]:
+        idx = np.random.default_rng(seed).choice(x.shape[0], size=n, replace=False)
+        x_query = x[idx, ...]
+    else:
+        x_query = x
+    return float(np.mean(local_dimensionality(x, k=k, x_query=x_query)))
 
 
 def compute_mu(nn_distances, d):
@@ -341,6 +364,19 @@ def compute_initial_value(nn_distances, d, mu, L, row_stride=None, target=None):
     auto, offset = ridge_row_stride(fit.n, fit.m, with_offset=True)
     fit.precond_build(auto if row_stride is None else row_stride, offset, force=row_stride is not None)
     return fit.ridge_init(target)
+
+
+def compute_initial_dimensionalities(x, mu_dim, mu_dens, L, nn_distances, d):
+    """reference parameters.py:899-924: row 0 Ridge(fit_intercept=False) of log(d) - mu_dim on L, row 1 the density's
+    Ridge start with the per-cell d.  Both with the exact Gram over all cells (the reference's Ridge): the objective is
+    not convex in the log-dimensionality, so the start is part of the answer."""
+    target = np.log(np.asarray(d, dtype=np.float64)) - mu_dim
+    fit = _fit_of(L)
+    if target.size == 1:
+        target = np.full(fit.n, float(target))
+    dims = compute_initial_value(None, None, None, L, row_stride=1, target=np.ascontiguousarray(target))
+    dens = compute_initial_value(nn_distances, d, mu_dens, L, row_stride=1)
+    return np.stack([dims, dens])
 
 
 # -- thin helpers over a predictor (parameters.py:59-86) ---------------------------------------------------------

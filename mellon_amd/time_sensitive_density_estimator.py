@@ -9,8 +9,8 @@ from .base_model import DEFAULT_COV_FUNC
 from .density_estimator import DensityEstimator
 from .inference import (DEFAULT_INIT_LEARN_RATE, DEFAULT_JIT, DEFAULT_N_ITER, DEFAULT_OPTIMIZER,
                         compute_conditional_times)
-from .parameters import (DEFAULT_RANDOM_SEED, compute_average_cell_count, compute_cov_func, compute_d, compute_ls,
-                         compute_landmarks_rescale_time, compute_nn_distances_within_time_points)
+from .parameters import (DEFAULT_RANDOM_SEED, compute_average_cell_count, compute_cov_func, compute_d, compute_d_factal,
+                         compute_ls, compute_landmarks_rescale_time, compute_nn_distances_within_time_points)
 from .util import DEFAULT_JITTER
 from .validation import validate_nn_distances_sharded, validate_positive_float, validate_time_x
 
@@ -52,8 +52,11 @@ class TimeSensitiveDensityEstimator(DensityEstimator):
 
     def _compute_d(self):
         if self.d_method == "fractal":
-            raise NotImplementedError("d_method='fractal' is outside the accelerated path.")
-        d = self.d if self.d_method == "manual" else compute_d(self.x[:, :-1])
+            # time_sensitive_density_estimator.py:423-440: the fractal dimension of the state columns
+            self._require_single_process("d")
+            d = compute_d_factal(self.x[:, :-1])
+        else:
+            d = self.d if self.d_method == "manual" else compute_d(self.x[:, :-1])
         if np.ndim(d) == 0 and d > 50:
             raise ValueError("The detected dimensionality of the data is over 50, which is likely to cause "
                              f"numerical instability issues; explicitly pass d={self.d} if intended.")

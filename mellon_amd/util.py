@@ -1,4 +1,5 @@
-"""Host-side helpers mirroring mellon/util.py (NumPy only; no device code here)."""
+"""Host-side helpers mirroring mellon/util.py (NumPy only, except local_dimensionality, whose neighbour search and
+fractal-dimension fit run in libmellon_hip.so)."""
 import functools
 import inspect
 import logging
@@ -261,3 +262,22 @@ def make_multi_time_argument(func):
 
     wrapper.__signature__ = new_sig
     return wrapper
+
+
+def local_dimensionality(x, k=30, x_query=None, neighbor_idx=None):
+    """reference util.py:486-536: the local fractal dimension at each query -- the least-squares slope of
+    log(1 .. k(k-1)/2) on the sorted log pair distances among its k nearest rows of x (the query itself included when it
+    is a row of x).  The exact k-NN search (mln_knn) and the per-query fit (mln_local_dimensionality) run on the device;
+    k <= 64.  A neighbourhood with a zero pair distance gives NaN, as the reference's lstsq does."""
+    from . import _lib
+    x = x.to_host() if isinstance(x, _lib.DeviceArray) else x
+    x = np.ascontiguousarray(ensure_2d(np.asarray(x, dtype=np.float64)))
+    if k > x.shape[0]:
+        logger.warning(f"Number of nearest neighbors (k={k}) is greater than the number of samples ({x.shape[0]}). "
+                       "Setting k to the number of samples.")
+        k = x.shape[0]
+    ctx = _lib.default_context()
+    if neighbor_idx is None:
+        q = x if x_query is None else np.ascontiguousarray(ensure_2d(np.asarray(x_query, dtype=np.float64)))
+        _, neighbor_idx = ctx.knn(q, k, y=x)
+    return ctx.local_dimensionality(x, neighbor_idx)
