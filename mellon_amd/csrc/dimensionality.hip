@@ -217,7 +217,8 @@ __global__ __launch_bounds__(LD_WG) void k_local_dim(const double* __restrict__ 
       __syncthreads();
     }
   }
-  // slope of y = log(1..kc2) on a = log(distance): sum (a - abar)(y - ybar) / sum (a - abar)^2  (= what lstsq returns)
+  // slope of y = log(1..kc2) on A = [a, 1], a = log(distance), as lstsq returns it: the closed form
+  // sum (a - abar)(y - ybar) / sum (a - abar)^2 while A has full rank, the minimum-norm solution once it has rank 1
   double sa = 0.0, sy = 0.0;
   for (int p = tid; p < kc2; p += LD_WG) { sa += log(sd[p]); sy += log((double)(p + 1)); }
   const double abar = block_sum_ld(sa, red) / kc2;
@@ -231,8 +232,27 @@ __global__ __launch_bounds__(LD_WG) void k_local_dim(const double* __restrict__ 
   const double Sxy = block_sum_ld(sxy, red);
   const double Sxx = block_sum_ld(sxx, red);
   if (tid == 0) {
-    // one pair (k = 2): y = log 1 = 0 and lstsq's minimum-norm answer is slope 0 (NaN for a zero distance, like lstsq)
-    out[q] = (kc2 == 1) ? (isfinite(abar) ? 0.0 : __builtin_nan("")) : Sxy / Sxx;
+    // A^T A = [[p, qq], [qq, N]], p = sum a^2, qq = sum a, det = N Sxx; eigenvalues (p + N) / 2 +- disc.  lstsq's rank
+    // rule: s_min <= eps max(N, 2) s_max, i.e. det <= (tol lam1)^2.  Rank 1 (an equidistant neighbourhood, to rounding;
+    // always for k = 2): slope = v1[0] (v1 . A^T y) / lam1, v1 the top eigenvector, from whichever of its two closed
+    // forms has no cancellation.  A zero distance gives NaN, like the reference's lstsq.
+    const double N = (double)kc2;
+    const double p = fma(N * abar, abar, Sxx), qq = N * abar;
+    const double det = N * Sxx;
+    const double h = 0.5 * (p - N), disc = sqrt(fma(h, h, qq * qq));
+    const double lam1 = 0.5 * (p + N) + disc;
+    const double tol = __DBL_EPSILON__ * (kc2 > 2 ? N : 2.0) * lam1;
+    double r;
+    if (!isfinite(abar)) {
+      r = __builtin_nan("");
+    } else if (det > tol * tol) {
+      r = Sxy / Sxx;
+    } else {
+      const double v0 = h >= 0.0 ? disc + h : qq, v1 = h >= 0.0 ? qq : disc - h;
+      const double aty0 = fma(N * abar, ybar, Sxy), aty1 = N * ybar;   // A^T y = [sum a y, sum y]
+      r = v0 * fma(v0, aty0, v1 * aty1) / (fma(v0, v0, v1 * v1) * lam1);
+    }
+    out[q] = r;
   }
 }
 

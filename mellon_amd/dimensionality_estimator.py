@@ -21,6 +21,7 @@ from .validation import validate_array, validate_float, validate_k, validate_pos
 logger = logging.getLogger("mellon")
 
 LOCAL_DIM_K = 30      # neighbours of the local fractal dimension (util.local_dimensionality's default)
+KNN_MAX_K = 64        # the device k-NN search's limit (mln_knn)
 
 
 class DimensionalityEstimator(BaseEstimator):
@@ -64,18 +65,28 @@ class DimensionalityEstimator(BaseEstimator):
 
     # -- attribute computations (reference dimensionality_estimator.py:345-467) --------------------------------
     def _compute_distances(self):
-        """The k nearest other cells (dimensionality_estimator.py:375-384), from ONE exact device search with
-        max(k + 1, 30) neighbours that also gives the local dimension its neighbourhoods: column 0 is the cell itself
-        (or a coincident cell, at distance 0), columns 1 .. k are the distances."""
+        """The k nearest other cells (dimensionality_estimator.py:375-384).  While k + 1 <= 64 (the device search's
+        limit), ONE exact device search with max(k + 1, 30) neighbours also gives the local dimension its neighbourhoods:
+        column 0 is the cell itself (or a coincident cell, at distance 0), columns 1 .. k are the distances.  At k = 64
+        the distances come from a search of k that skips the cell itself (the same multiset of distances), and the
+        neighbourhoods from a search of their own."""
+        if isinstance(self.k, (int, np.integer)) and self.k > KNN_MAX_K:
+            raise ValueError(f"k={self.k}: the exact device k-NN search finds at most {KNN_MAX_K} neighbours per cell, "
+                             f"so DimensionalityEstimator needs 1 <= k <= {KNN_MAX_K}.")
         logger.info("Computing distances.")
         from . import _lib
         x = self._host_x()
         n = x.shape[0]
         validate_k(self.k, n)
-        kk = max(self.k + 1, min(LOCAL_DIM_K, n))
-        dist, idx = _lib.default_context().knn(x, kk, return_index=True)
-        self._knn_idx = (self.x, idx[:, :min(LOCAL_DIM_K, n)])
-        return np.ascontiguousarray(dist[:, 1:self.k + 1])
+        ctx = _lib.default_context()
+        kl = min(LOCAL_DIM_K, n)
+        if self.k + 1 <= KNN_MAX_K:
+            dist, idx = ctx.knn(x, max(self.k + 1, kl), return_index=True)
+            self._knn_idx = (self.x, idx[:, :kl])
+            return np.ascontiguousarray(dist[:, 1:self.k + 1])
+        dist = ctx.knn(x, self.k, exclude_self=True, return_index=False)
+        self._knn_idx = (self.x, ctx.knn(x, kl, return_index=True)[1])
+        return np.ascontiguousarray(dist)
 
     def _compute_nn_distances(self):
         nn = np.ascontiguousarray(np.asarray(self.distances, dtype=np.float64)[:, 0])

@@ -71,6 +71,41 @@ def slope_closed(nd):
     return np.sum(da * dy) / np.sum(da * da)
 
 
+def slope_rank_rule(nd):
+    """The device's rule (k_local_dim), restated: lstsq's rank test on A = [a, 1] from the 2 x 2 normal matrix
+    (s_min <= eps max(kc2, 2) s_max  <=>  det(A^T A) <= (eps max(kc2, 2) lam1)^2, det = kc2 Sxx), then the closed-form slope
+    at full rank or the minimum-norm solution v1 v1^T A^T y / lam1 at rank 1."""
+    a = np.log(np.sort(nd))
+    y = np.log(np.arange(1, nd.size + 1))
+    if not np.all(np.isfinite(a)):
+        return np.nan
+    N = float(a.size)
+    abar, ybar = a.mean(), y.mean()
+    da, dy = a - abar, y - ybar
+    sxx, sxy = np.sum(da * da), np.sum(da * dy)
+    p, q = sxx + N * abar * abar, N * abar
+    h = 0.5 * (p - N)
+    disc = np.hypot(h, q)
+    lam1 = 0.5 * (p + N) + disc
+    tol = np.finfo(np.float64).eps * max(N, 2.0) * lam1
+    if N * sxx > tol * tol:
+        return sxy / sxx
+    v = np.array([disc + h, q]) if h >= 0 else np.array([q, disc - h])
+    aty = np.array([sxy + N * abar * ybar, N * ybar])
+    return v[0] * (v @ aty) / ((v @ v) * lam1)
+
+
+def one_hot_rows(k):
+    """k rows of the identity: every pair distance is exactly sqrt(2)."""
+    return np.eye(k)
+
+
+def rotated_simplex(k, seed):
+    """The rows Q e_i of a random orthogonal Q (k x k): pair distances sqrt(2) up to rounding."""
+    Q = np.linalg.qr(np.random.default_rng(seed).normal(size=(k, k)))[0]
+    return np.ascontiguousarray(Q.T)
+
+
 def pair_distances(nb):
     """The k(k-1)/2 distances among the rows of one neighbourhood (k x d)."""
     i, j = np.triu_indices(nb.shape[0], k=1)

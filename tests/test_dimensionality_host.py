@@ -75,3 +75,57 @@ def test_closed_form_slope_equals_lstsq():
             nd = dr.pair_distances(nb)
             a, b = dr.slope_closed(nd), dr.slope_lstsq(nd)
             assert abs(a - b) <= 1e-12 * max(1.0, abs(b)), (k, d, a, b)
+
+
+def _slope_cases():
+    rng = np.random.default_rng(12)
+    for k in (2, 3, 10, 30, 64):
+        for d in (1, 2, 7, 50):
+            yield f"gauss k={k} d={d}", dr.pair_distances(rng.normal(size=(k, d)) * rng.uniform(0.1, 3))
+    for k in (3, 4, 10, 30, 64):
+        yield f"one-hot k={k}", dr.pair_distances(dr.one_hot_rows(k))
+        for s in range(3):
+            yield f"simplex k={k} seed={s}", dr.pair_distances(dr.rotated_simplex(k, s))
+            yield f"scaled simplex k={k} seed={s}", dr.pair_distances(dr.rotated_simplex(k, s) * 10.0 ** (s - 1))
+
+
+def test_rank_rule_slope_equals_lstsq():
+    """The device's rule (full rank: closed form; rank 1: minimum norm) is lstsq's, equidistant neighbourhoods included."""
+    for name, nd in _slope_cases():
+        a, b = dr.slope_rank_rule(nd), dr.slope_lstsq(nd)
+        assert np.isfinite(a) and abs(a - b) <= 1e-10 * max(1.0, abs(b)), (name, a, b)
+
+
+def test_equidistant_neighbourhoods_are_rank_deficient_for_lstsq():
+    """The closed form alone is not lstsq's answer on an equidistant neighbourhood (0 / 0 or rounding noise), and the
+    exact answer there is c ybar / (1 + c^2), c = log of the common distance."""
+    for k in (3, 4, 10, 30, 64):
+        kc2 = k * (k - 1) // 2
+        c = np.log(np.sqrt(2.0))
+        want = c * np.mean(np.log(np.arange(1, kc2 + 1))) / (1 + c * c)
+        for nb in (dr.one_hot_rows(k), dr.rotated_simplex(k, k)):
+            nd = dr.pair_distances(nb)
+            assert abs(dr.slope_lstsq(nd) - want) <= 1e-12 * abs(want)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                closed = dr.slope_closed(nd)
+            assert not abs(closed - want) <= 1e-3 * abs(want), (k, closed, want)
+
+
+def test_zero_distance_gives_nan():
+    nd = dr.pair_distances(np.array([[0.0, 1.0], [0.0, 1.0], [2.0, 0.5]]))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        assert np.isnan(dr.slope_rank_rule(nd)) and np.isnan(dr.slope_lstsq(nd))
+
+
+def test_estimator_rejects_k_beyond_the_search_limit_before_device_work(monkeypatch):
+    import mellon_amd
+    from mellon_amd import _lib
+
+    def no_device(*a, **kw):
+        raise AssertionError("device work before the k check")
+    monkeypatch.setattr(_lib, "default_context", no_device)
+    x = np.random.default_rng(0).normal(size=(100, 3))
+    with pytest.raises(ValueError, match="1 <= k <= 64"):
+        mellon_amd.DimensionalityEstimator(k=65).prepare_inference(x)
+    with pytest.raises(ValueError, match="1 <= k <= 64"):
+        mellon_amd.DimensionalityEstimator(k=90).fit(x)
