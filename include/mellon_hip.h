@@ -329,6 +329,16 @@ int mln_fit_set_likelihood(mln_fit* fit, const double* V, const double* Vdr, dou
 int mln_objective(mln_fit* fit, const double* z, double* loss, double* grad /* m */,
                   double* hess_diag /* m or NULL */);
 
+/* mln_objective at S points in one call (the Monte-Carlo step of optimizer="advi", inference.py:768-876):
+ * loss[s], grad[s][:] = mln_objective(fit, Z[s][:]).  Z, grad: S x m row-major (row s = sample s); loss: S.  Any S >= 1
+ * (chunks of 64 samples inside).  Same likelihood (mln_fit_set_likelihood), same all-reduce over ranks (one per chunk:
+ * the losses and the gradient block together), prior terms added once per sample.  No likelihood cap; a non-finite loss
+ * is returned as it comes.  Two passes over the n x m buffer per chunk instead of one per sample: F = B W and
+ * G = B^T (exp(F + mu + V) - 1) on the fp64 matrix cores (csrc/objective_batch.hip).  Every handle layout is batched:
+ * explicit and implicit factors, Nystroem projections, mln_fit_from_L, the full GP, any number of landmarks.
+ * Bit-reproducible from call to call. */
+int mln_objective_batch(mln_fit* fit, const double* Z, int32_t S, double* loss /* S */, double* grad /* S x m */);
+
 /* a-8: the MAP solve.  inference.minimize_lbfgsb (inference.py:272-288) is SciPy's L-BFGS-B without
  * bounds behind jaxopt.ScipyMinimize; this is the same limited-memory BFGS with the same stopping
  * tests (relative loss decrease <= ftol, max|grad| <= gtol, maxiter), run inside the library on the

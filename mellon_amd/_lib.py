@@ -109,6 +109,7 @@ SYMBOLS = [
                                 C.POINTER(_i32), C.POINTER(_i32)]),
     ("mln_fit_set_likelihood", C.c_int, [_vp, _dp, _dp, _dbl]),
     ("mln_objective", C.c_int, [_vp, _dp, C.POINTER(_dbl), _dp, _dp]),
+    ("mln_objective_batch", C.c_int, [_vp, _dp, _i32, _dp, _dp]),
     ("mln_fit_set_dim_likelihood", C.c_int, [_vp, _dp, _i32, _dbl, _dbl]),
     ("mln_dim_objective", C.c_int, [_vp, _dp, C.POINTER(_dbl), _dp, _dp]),
     ("mln_transform", C.c_int, [_vp, _dp, _dbl, _dp]),
@@ -1064,6 +1065,18 @@ class Fit:
         self._check(self.lib.mln_objective(self.handle, z.ctypes.data, C.byref(loss), grad.ctypes.data,
                                                _ptr(hess)))
         return (loss.value, grad, hess) if with_hess else (loss.value, grad)
+
+    def objective_batch(self, Z):
+        """(loss[S], grad[S, m]) of the objective at the S rows of Z in one call: two passes over the n x m buffer on the
+        matrix cores instead of S (mln_objective_batch)."""
+        Z = _f64(Z)
+        if Z.ndim != 2 or Z.shape[1] != self.m or Z.shape[0] < 1:
+            raise ValueError(f"Z has shape {Z.shape}, expected (S >= 1, {self.m})")
+        loss = np.empty(Z.shape[0], dtype=np.float64)
+        grad = np.empty(Z.shape, dtype=np.float64)
+        self._check(self.lib.mln_objective_batch(self.handle, Z.ctypes.data, int(Z.shape[0]), loss.ctypes.data,
+                                                 grad.ctypes.data))
+        return loss, grad
 
     def set_dim_likelihood(self, ell, mu_dim, mu_dens):
         """ell: n x k, log of the sorted k-NN distances + log(pi) / 2 (mln_fit_set_dim_likelihood)."""

@@ -305,7 +305,11 @@ class BaseEstimator:
             self.opt_state = results.opt_state
             self.losses = results.losses
         elif self.optimizer == "advi":
-            run_advi()
+            results = run_advi(self.loss_func, self.initial_value, n_iter=self.n_iter,
+                               init_learn_rate=self.init_learn_rate, jit=self.jit)
+            self.pre_transformation = results.pre_transformation
+            self.pre_transformation_std = results.pre_transformation_std
+            self.losses = results.losses
         elif self.optimizer == "L-BFGS-B":
             results = minimize_lbfgsb(self.loss_func, self.initial_value, jit=self.jit, options=self.lbfgsb_options)
             self.pre_transformation = results.pre_transformation

@@ -97,6 +97,12 @@ class LossFunc:
         self.n_eval += 1
         return self.fit.objective(z)
 
+    def value_and_grad_batch(self, Z):
+        """(loss[S], grad[S, m]) at the S rows of Z from one batched device call (run_advi's Monte-Carlo step)."""
+        Z = np.asarray(Z, dtype=np.float64)
+        self.n_eval += Z.shape[0]
+        return self.fit.objective_batch(Z)
+
     # preconditioned variable (include/mellon_hip.h: mln_objective_precond)
     def value_and_grad_u(self, u):
         self.n_eval += 1
@@ -246,13 +252,6 @@ def minimize_lbfgsb(loss_func, initial_value, jit=DEFAULT_JIT, options=None):
     return Results(res.x.reshape(z0.shape), res, float(res.fun))      # (SciPy works on a flat vector)
 
 
-def _unavailable_optimizer(name):
-    def f(*a, **k):
-        raise NotImplementedError(f"optimizer '{name}' is outside the accelerated path; use 'L-BFGS-B' "
-                                  "(the MAP optimum is unique, SURVEY.md S8a-7).")
-    return f
-
-
 def minimize_adam(loss_func, initial_value, n_iter=DEFAULT_N_ITER, init_learn_rate=DEFAULT_INIT_LEARN_RATE,
                   jit=DEFAULT_JIT):
     """inference.py:222-269: `n_iter` Adam steps (jax.example_libraries.optimizers.adam: b1 = 0.9, b2 = 0.999,
@@ -277,7 +276,54 @@ def minimize_adam(loss_func, initial_value, n_iter=DEFAULT_N_ITER, init_learn_ra
     return Results(z, (z, m1, m2), np.asarray(losses))
 
 
-run_advi = _unavailable_optimizer("advi")
+def advi_draws(t, nsamples, m):
+    """The standard-normal draws of ADVI step t, shape (nsamples, m).  The reference keys its stream by the step
+    (jax.random.PRNGKey(t), inference.py:849); so does this one, with NumPy's generator instead of JAX's: a fit is
+    reproducible run to run, but its draws are not the reference's."""
+    return np.random.default_rng(int(t)).standard_normal((int(nsamples), int(m)))
+
+
+def run_advi(loss_func, initial_parameters, n_iter=DEFAULT_N_ITER, init_learn_rate=DEFAULT_INIT_LEARN_RATE,
+             nsamples=DEFAULT_NUM_SAMPLES, jit=DEFAULT_JIT):
+    """inference.py:821-876: mean-field Gaussian q = N(mean, diag(exp(log_std))^2) fitted by `n_iter` Adam steps on the
+    Monte-Carlo estimate of -ELBO over `nsamples` draws per step.  Parameters (mean, log_std) start at
+    (initial_parameters, 0): the reference's `-10 * zeros_like(...)` is zero, so the initial std is 1.
+    Step t: z_s = mean + exp(log_std) * eps_s with eps = advi_draws(t, nsamples, m);
+      value      = mean_s[loss(z_s) + log q(z_s)],  log q(z_s) = sum_j(-eps_sj^2 / 2 - log_std_j - log(2 pi) / 2)
+      d / d mean = mean_s grad loss(z_s);  d / d log_std = exp(log_std) * mean_s(grad loss(z_s) * eps_s) - 1
+    (what jax.value_and_grad of inference.py:848-850 yields).  The `nsamples` losses and gradients of a step are ONE
+    batched device call (loss_func.value_and_grad_batch -> mln_objective_batch): two passes over the n x m buffer instead
+    of `nsamples`.  losses[t] is the value at the parameters before update t: -ELBO, as in the reference (whose
+    variable is misnamed `elbo`).  Returns (pre_transformation, pre_transformation_std = exp(log_std), losses)."""
+    batch = getattr(loss_func, "value_and_grad_batch", None)
+    if batch is None:
+        raise NotImplementedError("optimizer 'advi' needs a loss with value_and_grad_batch (compute_loss_func returns one); "
+                                  "it is not available for plain callables or the dimensionality loss.")
+    mean = np.array(initial_parameters, dtype=np.float64)
+    log_std = np.zeros_like(mean)
+    m = mean.size
+    b1, b2, eps_adam = 0.9, 0.999, 1e-8
+    m1 = [np.zeros_like(mean), np.zeros_like(mean)]
+    m2 = [np.zeros_like(mean), np.zeros_like(mean)]
+    losses = []
+    for t in range(int(n_iter)):
+        eps = advi_draws(t, nsamples, m)
+        std = np.exp(log_std)
+        value, g = batch(mean.reshape(1, -1) + std.reshape(1, -1) * eps)
+        logq = np.sum(-0.5 * np.square(eps) - log_std.reshape(1, -1) - 0.5 * np.log(2 * np.pi), axis=1)
+        losses.append(float(np.mean(value + logq)))
+        grads = (np.mean(g, axis=0).reshape(mean.shape), (std.ravel() * np.mean(g * eps, axis=0) - 1.0).reshape(mean.shape))
+        rate = np.exp(-1e-2 * t) * init_learn_rate
+        params = [mean, log_std]
+        for leaf in range(2):
+            m1[leaf] = (1 - b1) * grads[leaf] + b1 * m1[leaf]
+            m2[leaf] = (1 - b2) * np.square(grads[leaf]) + b2 * m2[leaf]
+            mhat = m1[leaf] / (1 - b1 ** (t + 1))
+            vhat = m2[leaf] / (1 - b2 ** (t + 1))
+            params[leaf] = params[leaf] - rate * mhat / (np.sqrt(vhat) + eps_adam)
+        mean, log_std = params
+    Results = namedtuple("Results", "pre_transformation pre_transformation_std losses")
+    return Results(mean, np.exp(log_std), losses)
 
 
 def compute_laplace_std(loss_func, pre_transformation, jit=DEFAULT_JIT):
