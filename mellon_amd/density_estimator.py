@@ -71,9 +71,10 @@ class DensityEstimator(BaseEstimator):
     # -- attribute computations (reference density_estimator.py:311-402) --------------------------------
     def _compute_d(self):
         if self.d_method == "fractal":
-            # parameters.compute_d_factal: the mean local dimension of 500 cells (NumPy's draw, not JAX's: see there)
-            self._require_single_process("d")
-            d = compute_d_factal(self.x)
+            # parameters.compute_d_factal: the mean local dimension of 500 cells (NumPy's draw, not JAX's: see there).
+            # Sharded: every rank evaluates it on the cells of ALL ranks (the draw indexes the global cell set) -- the
+            # same kernels on the same data, so the same value everywhere, and no collective beyond the gather.
+            d = compute_d_factal(self._all_cells()[0])
         else:
             d = self.d if self.d_method == "manual" else compute_d(self.x)
         logger.info(f"Using d={d}.")

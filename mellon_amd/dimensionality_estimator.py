@@ -5,7 +5,13 @@ the (log-dimensionality, log-density) pair run on the MI355X; SciPy's L-BFGS-B d
 
 Deliberate deviation: duplicate cells give a zero nearest-neighbour distance and log 0 in the likelihood; the reference's
 solve then sees an infinite loss and stops where it started.  This estimator raises a ValueError naming the count of
-zero distances (or of non-finite local dimensions) before the solve instead."""
+zero distances (or of non-finite local dimensions) before the solve instead.
+
+Cells sharded over the ranks of a communicator (distributed.current(), contiguous shards in rank order): every rank
+searches ITS cells among the cells of ALL ranks (gathered once over the host communicator), so `distances`, `d`,
+`nn_distances`, `local_dim_x` and `log_density_x` are this rank's rows of the single-rank arrays; the heuristics, the
+landmarks, `Lp`, `pre_transformation` and both predictors are replicated.  Every decision (k, gp_type, n_landmarks, the
+duplicate-cell errors) is taken on global counts, so all ranks raise -- or go on -- together."""
 import logging
 
 import numpy as np
@@ -14,7 +20,9 @@ from .base_model import BaseEstimator, DEFAULT_COV_FUNC
 from .inference import (DEFAULT_INIT_LEARN_RATE, DEFAULT_JIT, DEFAULT_N_ITER, DEFAULT_OPTIMIZER,
                         compute_conditional, compute_conditional_explog, compute_dimensionality_loss_func,
                         compute_dimensionality_transform, compute_log_density_x)
-from .parameters import DEFAULT_RANDOM_SEED, compute_initial_dimensionalities, compute_mu
+from .parameter_validation import validate_params
+from .parameters import (DEFAULT_RANDOM_SEED, compute_gp_type, compute_initial_dimensionalities, compute_mu,
+                         compute_n_landmarks)
 from .util import DEFAULT_JITTER, ensure_2d
 from .validation import validate_array, validate_float, validate_k, validate_positive_int
 
@@ -22,6 +30,13 @@ logger = logging.getLogger("mellon")
 
 LOCAL_DIM_K = 30      # neighbours of the local fractal dimension (util.local_dimensionality's default)
 KNN_MAX_K = 64        # the device k-NN search's limit (mln_knn)
+
+
+def _count_over_ranks(count):
+    """A per-rank count of offending cells summed over the ranks: an error decided on the sum is raised by every rank
+    (one raised by a single rank would leave the others waiting in the next collective).  Single rank: the count."""
+    from .distributed import current
+    return current().global_count(int(count))
 
 
 class DimensionalityEstimator(BaseEstimator):
@@ -75,22 +90,33 @@ class DimensionalityEstimator(BaseEstimator):
                              f"so DimensionalityEstimator needs 1 <= k <= {KNN_MAX_K}.")
         logger.info("Computing distances.")
         from . import _lib
-        x = self._host_x()
-        n = x.shape[0]
-        validate_k(self.k, n)
+        # queries: this rank's cells; candidates: the cells of all ranks.  Indices are global (global_offset + local).
+        x, y, lo = self._queries_and_candidates()
+        n = x.shape[0] if y is None else y.shape[0]
+        validate_k(self.k, n)              # against the GLOBAL count: a shard with fewer than k cells is legal
         ctx = _lib.default_context()
         kl = min(LOCAL_DIM_K, n)
         if self.k + 1 <= KNN_MAX_K:
-            dist, idx = ctx.knn(x, max(self.k + 1, kl), return_index=True)
+            dist, idx = ctx.knn(x, max(self.k + 1, kl), y=y, return_index=True)
             self._knn_idx = (self.x, idx[:, :kl])
             return np.ascontiguousarray(dist[:, 1:self.k + 1])
-        dist = ctx.knn(x, self.k, exclude_self=True, return_index=False)
-        self._knn_idx = (self.x, ctx.knn(x, kl, return_index=True)[1])
+        dist = ctx.knn(x, self.k, y=y, exclude_self=True, self_offset=lo, return_index=False)
+        self._knn_idx = (self.x, ctx.knn(x, kl, y=y, return_index=True)[1])
         return np.ascontiguousarray(dist)
+
+    def _queries_and_candidates(self):
+        """(this rank's cells, the cells of all ranks, the global index of this rank's first cell); single rank:
+        (x, None, 0) -- the search then runs on x against itself."""
+        from .distributed import current
+        x = self._host_x()
+        if current().world_size == 1:
+            return x, None, 0
+        x_all, lo = self._all_cells()
+        return x, np.ascontiguousarray(ensure_2d(x_all)), lo
 
     def _compute_nn_distances(self):
         nn = np.ascontiguousarray(np.asarray(self.distances, dtype=np.float64)[:, 0])
-        zeros = int(np.count_nonzero(nn <= 0))
+        zeros = _count_over_ranks(np.count_nonzero(nn <= 0))
         if zeros:
             raise ValueError(f"{zeros} cells have a nearest-neighbour distance of 0 (duplicate cells): the likelihood "
                              "takes its logarithm. Remove or jitter the duplicates.")
@@ -99,16 +125,29 @@ class DimensionalityEstimator(BaseEstimator):
     def _compute_d(self):
         from .util import local_dimensionality
         held = self.__dict__.pop("_knn_idx", None)
-        x = self._host_x()
+        x, y, _ = self._queries_and_candidates()
         if held is not None and held[0] is self.x:
-            d = local_dimensionality(x, k=held[1].shape[1], neighbor_idx=held[1])
-        else:
+            # the neighbourhoods hold global indices: rows of the cells of all ranks
+            d = local_dimensionality(x if y is None else y, k=held[1].shape[1], neighbor_idx=held[1])
+        elif y is None:
             d = local_dimensionality(x)
-        bad = int(np.count_nonzero(~np.isfinite(d)))
+        else:
+            d = local_dimensionality(y, x_query=x)
+        bad = _count_over_ranks(np.count_nonzero(~np.isfinite(d)))
         if bad:
             raise ValueError(f"{bad} cells have a non-finite local dimension (a zero distance among their "
                              f"{LOCAL_DIM_K} nearest neighbours: duplicate cells). Remove or jitter the duplicates.")
         return d
+
+    # decisions on the cells of ALL ranks: a small shard must not pick a gp type (or a landmark count) of its own
+    def _compute_n_landmarks(self):
+        return compute_n_landmarks(self.gp_type, self._n_cells_global(), self.landmarks)
+
+    def _compute_gp_type(self):
+        return compute_gp_type(self.n_landmarks, self.rank, self._n_cells_global())
+
+    def validate_parameter(self):
+        validate_params(self.rank, self.gp_type, self._n_cells_global(), self.n_landmarks, self.landmarks)
 
     def _compute_mu_dens(self):
         return compute_mu(self.nn_distances, self.d)
@@ -158,10 +197,6 @@ class DimensionalityEstimator(BaseEstimator):
             x = self.x
         elif self.x is not None and self.x is not x:
             raise ValueError("self.x has been set already, but is not equal to the argument x.")
-        from .distributed import current
-        if current().world_size > 1:
-            raise NotImplementedError("DimensionalityEstimator does not support cells sharded over several ranks: "
-                                      "fit it in a single process with all cells.")
         self.set_x(x)
         from .util import log_nn_new_fit
         log_nn_new_fit()

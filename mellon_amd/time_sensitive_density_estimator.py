@@ -52,9 +52,9 @@ class TimeSensitiveDensityEstimator(DensityEstimator):
 
     def _compute_d(self):
         if self.d_method == "fractal":
-            # time_sensitive_density_estimator.py:423-440: the fractal dimension of the state columns
-            self._require_single_process("d")
-            d = compute_d_factal(self.x[:, :-1])
+            # time_sensitive_density_estimator.py:423-440: the fractal dimension of the state columns (of the cells of
+            # all ranks when sharded: every rank evaluates the same draw on the same data)
+            d = compute_d_factal(self._all_cells()[0][:, :-1])
         else:
             d = self.d if self.d_method == "manual" else compute_d(self.x[:, :-1])
         if np.ndim(d) == 0 and d > 50:
