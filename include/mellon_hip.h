@@ -104,6 +104,10 @@ int mln_host_unregister(mln_ctx* ctx, const void* host_ptr);
  * allocator so that repeated fits do not pay hipMalloc / page-mapping again; this returns all
  * cached blocks to the driver.                                                                */
 int mln_release_cached_memory(void);
+/* Read-only view of that allocator (process-wide, no context): out[0] device blocks handed out and not yet released,
+ * out[1] their bytes as recorded, out[2] pinned host blocks handed out, out[3] bytes sitting in the device cache,
+ * out[4] successful hipMalloc calls since load.  Memory from mln_malloc is not counted.       */
+int mln_diag_alloc_stats(int64_t* out);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ------------------------------------------
  * Cells (rows of x) are sharded; landmarks, Lp and z are replicated.  Collectives: all-reduce

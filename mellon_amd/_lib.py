@@ -63,6 +63,7 @@ SYMBOLS = [
     ("mln_host_register", C.c_int, [_vp, _vp, _i64]),
     ("mln_host_unregister", C.c_int, [_vp, _vp]),
     ("mln_release_cached_memory", C.c_int, []),
+    ("mln_diag_alloc_stats", C.c_int, [_vp]),
     ("mln_comm_unique_id", C.c_int, [_vp]),
     ("mln_comm_init", C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     ("mln_comm_allreduce_sum", C.c_int, [_vp, _dp, _i64]),
@@ -1171,6 +1172,16 @@ class Fit:
 def release_cached_memory():
     """Return the library's cached device blocks to the driver."""
     load_library().mln_release_cached_memory()
+
+
+def alloc_stats():
+    """The caching allocator's books (process-wide): blocks handed out and cached.  ``DeviceArray`` memory is not counted."""
+    out = (C.c_int64 * 5)()
+    rc = load_library().mln_diag_alloc_stats(out)
+    if rc != 0:
+        raise MellonHipError(f"mln_diag_alloc_stats failed ({rc})")
+    keys = ["live_blocks", "live_bytes", "live_pinned_blocks", "cached_bytes", "driver_allocs"]
+    return dict(zip(keys, [int(v) for v in out]))
 
 
 _default_ctx = None

@@ -20,6 +20,7 @@ const bool g_enabled = (std::getenv("MELLON_AMD_NO_CACHE") == nullptr);
 // MELLON_AMD_POISON=1 (debugging): every block handed out is filled with 0xFF bytes first (NaN as a double, -1 as an
 // integer), so that a kernel reading memory nobody wrote shows up in the results instead of depending on what the
 // block held before.
+int64_t g_driver_allocs = 0;   // successful hipMalloc calls since load (mln_diag_alloc_stats)
 const bool g_poison = (std::getenv("MELLON_AMD_POISON") != nullptr && std::atoi(std::getenv("MELLON_AMD_POISON")) != 0);
 
 void flush_locked() {
@@ -52,17 +53,10 @@ hipError_t mln_dmalloc(void** out, size_t bytes) {
     flush_locked();
     e = hipMalloc(out, bytes);
   }
-  if (e == hipSuccess) g_live[*out] = {bytes, dev};
+  if (e == hipSuccess) { g_live[*out] = {bytes, dev}; ++g_driver_allocs; }
   if (e == hipSuccess && g_poison) { (void)hipMemset(*out, 0xFF, bytes); (void)hipDeviceSynchronize(); }
   return e;
 }
-
-// Deferred frees of the calling thread (mln_dfree_defer): a chain that runs on a side stream NEXT TO a long kernel must not
-// sit out that kernel in the device-wide synchronisation of every temporary it releases.
-namespace {
-thread_local std::vector<void*>* t_deferred = nullptr;
-}
-void mln_dfree_defer(std::vector<void*>* sink) { t_deferred = sink; }
 
 namespace {
 hipError_t release_block(void* p);
@@ -70,7 +64,6 @@ hipError_t release_block(void* p);
 
 hipError_t mln_dfree(void* p) {
   if (!p) return hipSuccess;
-  if (t_deferred) { t_deferred->push_back(p); return hipSuccess; }
   (void)hipDeviceSynchronize();  // same guarantee hipFree gives: nothing in flight touches the block
   return release_block(p);
 }
@@ -79,7 +72,6 @@ hipError_t mln_dfree(void* p) {
 // runs beside another context's long kernel (k-means landmarks beside the 1-NN search) does not sit that kernel out.
 hipError_t mln_dfree_synced(void* p) {
   if (!p) return hipSuccess;
-  if (t_deferred) { t_deferred->push_back(p); return hipSuccess; }
   return release_block(p);
 }
 
@@ -146,4 +138,20 @@ void mln_dcache_flush() {
   std::lock_guard<std::mutex> lk(g_hmu);
   for (auto& kv : g_hfree) (void)hipHostFree(kv.second);
   g_hfree.clear();
+}
+
+// Read-only view of both pools (process-wide, like the flush above): what is handed out, what is cached.
+extern "C" int mln_diag_alloc_stats(int64_t* out) {
+  if (!out) return MLN_ERR_ARG;
+  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> hlk(g_hmu);
+  int64_t live = 0, cached = 0;
+  for (const auto& kv : g_live) live += (int64_t)kv.second.first;
+  for (const auto& kv : g_free) cached += (int64_t)kv.first;
+  out[0] = (int64_t)g_live.size();
+  out[1] = live;
+  out[2] = (int64_t)g_hlive.size();
+  out[3] = cached;
+  out[4] = g_driver_allocs;
+  return MLN_OK;
 }

@@ -33,12 +33,13 @@ bool is_device_ptr(const void* p) {
 
 int mln_scratch(mln_ctx* ctx, size_t bytes, void** out) {
   if (bytes > ctx->scratch_bytes) {
-    if (ctx->scratch) { MLN_HIP(ctx, hipStreamSynchronize(ctx->stream)); MLN_HIP(ctx, mln_dfree(ctx->scratch)); ctx->scratch = nullptr; }
+    if (ctx->scratch) { MLN_HIP(ctx, hipStreamSynchronize(ctx->stream)); ctx->scratch.reset(); }
     size_t want = bytes + bytes / 4 + 4096;
-    MLN_HIP(ctx, mln_dmalloc(&ctx->scratch, want));
+    ctx->scratch_bytes = 0;
+    MLN_TRY(ctx->scratch.alloc(ctx, want, "scratch"));
     ctx->scratch_bytes = want;
   }
-  *out = ctx->scratch;
+  *out = ctx->scratch.get();
   return MLN_OK;
 }
 
@@ -112,7 +113,7 @@ extern "C" int mln_ctx_create(int device, mln_ctx** out) {
   ctx->device = device;
   ctx->n_cu = prop.multiProcessorCount;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&ctx->stream) != hipSuccess ||
-      mln_dmalloc((void**)&ctx->d_info, 4 * sizeof(int)) != hipSuccess) {
+      ctx->d_info.alloc(ctx, 4, "d_info") != MLN_OK) {
     mln_set_error(nullptr, "failed to initialise the HIP context");
     delete ctx;
     return MLN_ERR_HIP;
@@ -129,8 +130,8 @@ extern "C" void mln_ctx_destroy(mln_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   comm_release(ctx);
   fit_release_copy_lane(ctx);
-  if (ctx->scratch) (void)mln_dfree(ctx->scratch);
-  if (ctx->d_info) (void)mln_dfree(ctx->d_info);
+  ctx->scratch.reset();
+  ctx->d_info.reset();
   (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -319,10 +320,10 @@ extern "C" int mln_kernel_gram(mln_ctx* ctx, const mln_kernel_desc* cov, const d
   MLN_TRY(o.init(ctx, out, (size_t)m * m));
   const int64_t ld = pad16(m);
   const int64_t chunk = (n < 65536) ? (n > 0 ? n : 1) : 65536;
-  double *K = nullptr, *G = nullptr, *acc = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&K, sizeof(double) * (size_t)chunk * ld));
-  MLN_HIP(ctx, mln_dmalloc((void**)&G, sizeof(double) * (size_t)m * ld));
-  MLN_HIP(ctx, mln_dmalloc((void**)&acc, sizeof(double) * (size_t)m * ld));
+  DevBuf<double> K, G, acc;
+  MLN_TRY(K.alloc(ctx, (size_t)chunk * ld, "K"));
+  MLN_TRY(G.alloc(ctx, (size_t)m * ld, "G"));
+  MLN_TRY(acc.alloc(ctx, (size_t)m * ld, "acc"));
   int rc = (hipMemsetAsync(acc, 0, sizeof(double) * (size_t)m * ld, ctx->stream) == hipSuccess) ? MLN_OK : MLN_ERR_HIP;
   bool any = false;
   for (int64_t r0 = 0; (r0 < n || !any) && rc == MLN_OK; r0 += chunk) {   // at least one (possibly empty) round: collectives
@@ -336,7 +337,6 @@ extern "C" int mln_kernel_gram(mln_ctx* ctx, const mln_kernel_desc* cov, const d
   if (rc == MLN_OK) rc = launch_copy_block(ctx, acc, ld, o.dev, m, m, m);
   if (rc == MLN_OK) rc = o.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(K); (void)mln_dfree(G); (void)mln_dfree(acc);
   return rc;
 }
 
@@ -385,7 +385,6 @@ extern "C" int mln_trsm_lower(mln_ctx* ctx, const double* Lf, int64_t m, int32_t
   int rc = trans == 0 ? triinv_solve_left(ctx, t, b.dev, p, p) : triinv_solve_left_T(ctx, t, b.dev, p, p);
   if (rc == MLN_OK) rc = b.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  triinv_free(&t);
   return rc;
 }
 
@@ -439,10 +438,10 @@ extern "C" int mln_gemm(mln_ctx* ctx, int32_t ta, int32_t tb, int64_t M, int64_t
   if (a_dev) da.dev = A;
   if (b_dev) db.dev = B;
   double* Cd = Cm;
-  double* c_owned = nullptr;
+  DevBuf<double> c_owned;
   if (!c_dev) {
     ldc_d = (N + 1) & ~(int64_t)1;
-    MLN_HIP(ctx, mln_dmalloc((void**)&c_owned, sizeof(double) * (size_t)M * ldc_d));
+    MLN_TRY(c_owned.alloc(ctx, (size_t)M * ldc_d, "c_owned"));
     Cd = c_owned;
     if (beta != 0.0)
       MLN_HIP(ctx, hipMemcpy2DAsync(Cd, sizeof(double) * ldc_d, Cm, sizeof(double) * ldc, sizeof(double) * N, (size_t)M, hipMemcpyHostToDevice, ctx->stream));
@@ -460,7 +459,6 @@ extern "C" int mln_gemm(mln_ctx* ctx, int32_t ta, int32_t tb, int64_t M, int64_t
     if (e != hipSuccess) rc = mln_hip_fail(ctx, e, "mln_gemm download", __FILE__, __LINE__);
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (c_owned) (void)mln_dfree(c_owned);
   return rc;
 }
 
@@ -474,15 +472,15 @@ extern "C" int mln_eigh(mln_ctx* ctx, const double* A, int64_t m, double* w, dou
   DevOut v;
   MLN_TRY(a.init(ctx, A, (size_t)m * m));
   MLN_TRY(v.init(ctx, V, (size_t)m * m));
-  double* rows = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&rows, sizeof(double) * (size_t)m * m));
+  DevBuf<double> rows;
+  MLN_TRY(rows.alloc(ctx, (size_t)m * m, "rows"));
   std::vector<double> wh((size_t)m);
   int sweeps = 0;
   int rc = dev_eigh(ctx, a.dev, m, m, wh.data(), rows, m, &sweeps);
   if (rc == MLN_OK) rc = launch_transpose(ctx, rows, m, v.dev, m, m);   // eigenvectors as columns
   if (rc == MLN_OK) rc = v.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(rows);
+  rows.reset();
   if (rc != MLN_OK) return rc;
   if (n_sweeps) *n_sweeps = sweeps;
   if (is_device_ptr(w)) MLN_HIP(ctx, hipMemcpy(w, wh.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice));
@@ -517,13 +515,13 @@ extern "C" int mln_predict_mean(mln_ctx* ctx, const mln_kernel_desc* cov, const 
   chunk = (chunk / 128) * 128;
   if (chunk < 128) chunk = 128;
   if (chunk > n_new) chunk = n_new;
-  double* Kc = nullptr;
-  double* mus = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&Kc, sizeof(double) * (size_t)chunk * m));
+  DevBuf<double> Kc;
+  DevBuf<double> mus;
+  MLN_TRY(Kc.alloc(ctx, (size_t)chunk * m, "Kc"));
   int rc = MLN_OK;
   if (mu != 0.0) {
     std::vector<double> h((size_t)(chunk * p), mu);
-    rc = (mln_dmalloc((void**)&mus, sizeof(double) * h.size()) == hipSuccess &&
+    rc = (mus.alloc(ctx, h.size(), "mus") == MLN_OK &&
           hipMemcpy(mus, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) == hipSuccess) ? MLN_OK : MLN_ERR_HIP;
   }
   for (int64_t r0 = 0; r0 < n_new && rc == MLN_OK; r0 += chunk) {
@@ -544,8 +542,6 @@ extern "C" int mln_predict_mean(mln_ctx* ctx, const mln_kernel_desc* cov, const 
   }
   if (rc == MLN_OK) rc = o.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(Kc);
-  if (mus) (void)mln_dfree(mus);
   return rc;
 }
 
@@ -574,11 +570,10 @@ extern "C" int mln_predict_covariance(mln_ctx* ctx, const mln_kernel_desc* cov, 
   int64_t chunk = diag ? (int64_t)((1ull << 30) / (sizeof(double) * (size_t)ld)) : n_new;
   if (chunk > n_new) chunk = n_new;
   if (chunk < 1) chunk = 1;
-  double *A = nullptr, *kss = nullptr;
+  DevBuf<double> A, kss;
   int rc = MLN_OK;
-  auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "predict_covariance", __FILE__, __LINE__); };
-  chk(mln_dmalloc((void**)&A, sizeof(double) * (size_t)chunk * ld));
-  chk(mln_dmalloc((void**)&kss, sizeof(double) * (size_t)chunk));
+  if (rc == MLN_OK) rc = A.alloc(ctx, (size_t)chunk * ld, "A");
+  if (rc == MLN_OK) rc = kss.alloc(ctx, (size_t)chunk, "kss");
   for (int64_t r0 = 0; r0 < n_new && rc == MLN_OK; r0 += chunk) {
     const int64_t rows = (n_new - r0 < chunk) ? (n_new - r0) : chunk;
     rc = launch_kernel_matrix(ctx, dc, dx.dev + r0 * d, rows, dcen.dev, m, d, A, ld, 0.0);
@@ -597,9 +592,6 @@ extern "C" int mln_predict_covariance(mln_ctx* ctx, const mln_kernel_desc* cov, 
   }
   if (rc == MLN_OK) rc = o.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  triinv_free(&t);
-  if (A) (void)mln_dfree(A);
-  if (kss) (void)mln_dfree(kss);
   return rc;
 }
 
@@ -625,11 +617,10 @@ extern "C" int mln_predict_mean_covariance(mln_ctx* ctx, const mln_kernel_desc* 
   int64_t chunk = diag ? (int64_t)((1ull << 30) / (sizeof(double) * (size_t)(m + ldq))) : n_new;
   if (chunk > n_new) chunk = n_new;
   if (chunk < 1) chunk = 1;
-  double *Kc = nullptr, *T = nullptr;
+  DevBuf<double> Kc, T;
   int rc = MLN_OK;
-  auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "predict_mean_covariance", __FILE__, __LINE__); };
-  chk(mln_dmalloc((void**)&Kc, sizeof(double) * (size_t)chunk * m));
-  chk(mln_dmalloc((void**)&T, sizeof(double) * (size_t)chunk * ldq));
+  if (rc == MLN_OK) rc = Kc.alloc(ctx, (size_t)chunk * m, "Kc");
+  if (rc == MLN_OK) rc = T.alloc(ctx, (size_t)chunk * ldq, "T");
   for (int64_t r0 = 0; r0 < n_new && rc == MLN_OK; r0 += chunk) {
     const int64_t rows = (n_new - r0 < chunk) ? (n_new - r0) : chunk;
     rc = launch_kernel_matrix(ctx, dc, dx.dev + r0 * d, rows, dcen.dev, m, d, Kc, m, 0.0);
@@ -649,8 +640,6 @@ extern "C" int mln_predict_mean_covariance(mln_ctx* ctx, const mln_kernel_desc* 
   }
   if (rc == MLN_OK) rc = o.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  if (Kc) (void)mln_dfree(Kc);
-  if (T) (void)mln_dfree(T);
   return rc;
 }
 

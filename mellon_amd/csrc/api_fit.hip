@@ -1,6 +1,7 @@
 // C ABI, part 2: the fit handle (see api_internal.h for the map of the api*.hip files).
 #include "api_internal.h"
 #include "mln_options.h"
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 
@@ -11,30 +12,17 @@ void fit_sample_rows(const mln_fit* f, int64_t s, int64_t* first, int64_t* rows)
   *rows = (f->n > *first) ? (f->n - *first + s - 1) / s : 0;
 }
 
-void fit_free(mln_fit* f) {
-  if (!f) return;
-  mln_ctx* ctx = f->ctx;
+// the members release themselves; a handle whose ctx was never set holds nothing
+mln_fit::~mln_fit() {
+  if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  if (f->L && f->L != f->Lp) (void)mln_dfree(f->L);
-  if (f->Lp) (void)mln_dfree(f->Lp);
-  triinv_free(&f->tri);
-  void* ptrs[] = {f->V, f->Vdr, f->part_grad, f->part_hess, f->part_loss, f->d_z, f->d_out,
-                  f->C, f->Cinv, f->d_u, f->d_gu, f->d_tmp, f->P, f->d_w, f->d_w_cached,
-                  f->Q1, f->Q2, f->d_zw, f->d_zr, f->eigU, f->L32, f->sv_block, f->f_keep[0], f->f_keep[1], f->Kj, f->d_over,
-                  f->dim_ell, f->dim_part, f->dim_z, f->dim_out};
-  for (void* p : ptrs) if (p) (void)mln_dfree(p);
-  for (double* p : f->saved_precond) if (p) (void)mln_dfree(p);
-  if (f->h_state) (void)mln_hfree(f->h_state);
-  fit_events_return(ctx, &f->evs);
-  if (f->h_z) (void)mln_hfree(f->h_z);
-  if (f->h_out) (void)mln_hfree(f->h_out);
-  if (f->ev0) (void)hipEventDestroy(f->ev0);
-  if (f->ev1) (void)hipEventDestroy(f->ev1);
-  delete f;
+  fit_events_return(ctx, &evs);
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
 }
 
-extern "C" void mln_fit_destroy(mln_fit* fit) { fit_free(fit); }
+extern "C" void mln_fit_destroy(mln_fit* fit) { delete fit; }
 
 int fit_alloc_workspace(mln_fit* f) {
   mln_ctx* ctx = f->ctx;
@@ -46,23 +34,21 @@ int fit_alloc_workspace(mln_fit* f) {
   n_wg = f->n_wg_cap;
   const size_t pm = (size_t)f->ldl;
   f->ld2 = pad16(f->m + 2);
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_u, sizeof(double) * pm));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_gu, sizeof(double) * pm));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_tmp, sizeof(double) * (1 + pm)));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_w, sizeof(double) * pm));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_w_cached, sizeof(double) * pm));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_zw, sizeof(double) * 2 * pm));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_zr, sizeof(double) * 2 * (size_t)f->ld2));
-  MLN_HIP(ctx, hipMemsetAsync(f->d_zr, 0, sizeof(double) * 2 * (size_t)f->ld2, ctx->stream));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_over, 64));
-  MLN_HIP(ctx, hipMemsetAsync(f->d_over, 0, 64, ctx->stream));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->part_grad, sizeof(double) * pm * n_wg));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->part_hess, sizeof(double) * pm * n_wg));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->part_loss, sizeof(double) * n_wg));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_z, sizeof(double) * pm));
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->d_out, sizeof(double) * (1 + 2 * pm)));
-  MLN_HIP(ctx, mln_hmalloc((void**)&f->h_z, sizeof(double) * pm));
-  MLN_HIP(ctx, mln_hmalloc((void**)&f->h_out, sizeof(double) * (1 + 2 * pm)));
+  MLN_TRY(f->d_u.alloc(ctx, pm, "d_u"));
+  MLN_TRY(f->d_gu.alloc(ctx, pm, "d_gu"));
+  MLN_TRY(f->d_tmp.alloc(ctx, (1 + pm), "d_tmp"));
+  MLN_TRY(f->d_w.alloc(ctx, pm, "d_w"));
+  MLN_TRY(f->d_w_cached.alloc(ctx, pm, "d_w_cached"));
+  MLN_TRY(f->d_zw.alloc(ctx, 2 * pm, "d_zw"));
+  MLN_TRY(f->d_zr.alloc_zeroed(ctx, 2 * (size_t)f->ld2, "d_zr"));
+  MLN_TRY(f->d_over.alloc_zeroed(ctx, 16, "d_over"));
+  MLN_TRY(f->part_grad.alloc(ctx, pm * n_wg, "part_grad"));
+  MLN_TRY(f->part_hess.alloc(ctx, pm * n_wg, "part_hess"));
+  MLN_TRY(f->part_loss.alloc(ctx, n_wg, "part_loss"));
+  MLN_TRY(f->d_z.alloc(ctx, pm, "d_z"));
+  MLN_TRY(f->d_out.alloc(ctx, (1 + 2 * pm), "d_out"));
+  MLN_TRY(f->h_z.alloc(ctx, pm, "h_z"));
+  MLN_TRY(f->h_out.alloc(ctx, (1 + 2 * pm), "h_out"));
   MLN_HIP(ctx, hipEventCreate(&f->ev0));
   MLN_HIP(ctx, hipEventCreate(&f->ev1));
   return MLN_OK;
@@ -100,7 +86,7 @@ static int copy_lane_get(mln_ctx* ctx, int n_events, hipStream_t* stream, std::v
 }
 
 // The per-evaluation timing events of the device-resident solver (three per evaluation, ~100 per fit) are the context's too:
-// a solve borrows them into its handle and hands them back (fit_free does so for a solve that ended early).
+// a solve borrows them into its handle and hands them back (~mln_fit does so for a solve that ended early).
 namespace {
 std::unordered_map<mln_ctx*, std::vector<hipEvent_t>> g_event_pools;
 }  // namespace
@@ -263,7 +249,7 @@ int fit_prepare_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, 
   bool pipelined = !f->full && n > 0 && x && !is_device_ptr(x) && (size_t)n * d * sizeof(double) >= ((size_t)32 << 20);
   if (pipelined) {
     dx.ctx = ctx;
-    MLN_HIP(ctx, mln_dmalloc((void**)&dx.owned, (size_t)n * d * sizeof(double)));
+    MLN_TRY(dx.owned.alloc(ctx, (size_t)n * d, "cells"));
     dx.dev = dx.owned;
     MLN_TRY(up.start(ctx, x, dx.owned, n, d));
     if (trace_all) fprintf(stderr, "[trace] fit_prepare: upload started at %.4f s (%d chunks)\n", now_s() - t_enter, up.n_chunks);
@@ -275,9 +261,8 @@ int fit_prepare_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, 
 
   // Lp = chol(cov(xu, xu) + max(sigma^2, jitter) I), sigma = 0     decomposition.py:111-123
   double t0 = now_s();
-  const size_t lp_bytes = sizeof(double) * (size_t)m * f->ldp;
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->Lp, lp_bytes));
-  MLN_HIP(ctx, hipMemsetAsync(f->Lp, 0, lp_bytes, ctx->stream));
+  const size_t lp_count = (size_t)m * f->ldp;
+  MLN_TRY(f->Lp.alloc_zeroed(ctx, lp_count, "Lp"));
   // (Round 4 built the landmark-only chain -- cov(xu, xu), its Cholesky factor, the block-scaled copies -- in a helper thread
   //  on a second stream UNDER the kernel-matrix pass on a CU-masked stream: 1.9 ms less kernel time, 2.3 ms more wall time;
   //  taken out in round 5, profiles/HISTORY.md.)
@@ -291,8 +276,8 @@ int fit_prepare_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, 
     const bool implicit = !f->full && (flags & MLN_FIT_IMPLICIT) != 0;
     if (implicit) {
       // Kj = cov(xu, xu) + jitter I survives the factorisation: the prior's Hessian in w-space (fit_build_precond)
-      MLN_HIP(ctx, mln_dmalloc((void**)&f->Kj, lp_bytes));
-      MLN_HIP(ctx, hipMemcpyAsync(f->Kj, f->Lp, lp_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+      MLN_TRY(f->Kj.alloc(ctx, lp_count, "Kj"));
+      MLN_HIP(ctx, hipMemcpyAsync(f->Kj, f->Lp, sizeof(double) * lp_count, hipMemcpyDeviceToDevice, ctx->stream));
     }
     MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
     f->times[0] += now_s() - t0;
@@ -314,9 +299,9 @@ int fit_prepare_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, 
   } else {
     // L = cov(x, xu) Lp^-T                                          decomposition.py:205-210
     t0 = now_s();
-    const size_t l_bytes = sizeof(double) * (size_t)(n > 0 ? n : 1) * f->ldl;
     const bool trace = std::getenv("MELLON_AMD_TRACE") != nullptr;
-    MLN_HIP(ctx, mln_dmalloc((void**)&f->L, l_bytes));
+    MLN_TRY(f->L_own.alloc(ctx, (size_t)(n > 0 ? n : 1) * f->ldl, "L"));
+    f->L = f->L_own;
     if (trace) { (void)hipStreamSynchronize(ctx->stream); fprintf(stderr, "[trace] L alloc %.4f s\n", now_s() - t0); }
     // Mixed precision (OPT-IN since round 5: MELLON_AMD_MIXED=1, large implicit fits): the kernel-matrix pass also writes
     // a 32-bit copy, which the first passes of the MAP solve stream instead of the fp64 one.  The product default is the
@@ -327,7 +312,7 @@ int fit_prepare_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, 
     if (const char* ev = std::getenv("MELLON_AMD_MIXED")) mixed = (flags & MLN_FIT_IMPLICIT) != 0 && std::atoi(ev) != 0;
     if (const char* ev = std::getenv("MELLON_AMD_MIXED_MIN_ELEMS")) mixed_min = std::atoll(ev);
     if (mixed && n * m >= mixed_min && n > 0 && m <= 8192)     // (beyond 8192 landmarks the pass is segmented: objective.hip)
-      MLN_HIP(ctx, mln_dmalloc((void**)&f->L32, sizeof(float) * (size_t)n * f->ldl));
+      MLN_TRY(f->L32.alloc(ctx, (size_t)n * f->ldl, "L32"));
     // Format of the copy.  Covariance values of stationary kernels and of their products lie in [0, 1]: there the
     // fixed-point number round(v 2^32) has an absolute error of 1.2e-10 for EVERY entry, where fp32 carries up to 3e-8
     // on the entries near 1 -- which, with the nearest-neighbour length-scale heuristic, are most of them.  The
@@ -384,12 +369,12 @@ extern "C" int mln_fit_prepare(mln_ctx* ctx, const mln_kernel_desc* cov, const d
   *out = nullptr;
   if (n_local < 0 || d < 1 || (n_local > 0 && !x)) { mln_set_error(ctx, "bad shape"); return MLN_ERR_SHAPE; }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
-  mln_fit* f = new mln_fit();
+  std::unique_ptr<mln_fit> f(new mln_fit());
   const double t_call = now_s();
-  int rc = fit_prepare_impl(ctx, cov, x, n_local, d, xu, m, jitter, Lp_in, flags, f);
+  int rc = fit_prepare_impl(ctx, cov, x, n_local, d, xu, m, jitter, Lp_in, flags, f.get());
   if (std::getenv("MELLON_AMD_TRACE")) fprintf(stderr, "[trace] mln_fit_prepare: %.4f s with the upload's teardown\n", now_s() - t_call);
-  if (rc != MLN_OK) { fit_free(f); return rc; }
-  *out = f;
+  MLN_TRY(rc);
+  *out = f.release();
   return MLN_OK;
 }
 
@@ -400,31 +385,24 @@ extern "C" int mln_fit_from_L(mln_ctx* ctx, const double* L, int64_t n_local, in
   if (n_local < 1 || m < 1 || m > 65535) { mln_set_error(ctx, "bad shape"); return MLN_ERR_SHAPE; }
   if (m > objective_max_m()) { mln_set_error(ctx, "m > 8192 columns is not supported by this build"); return MLN_ERR_UNSUPPORTED; }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
-  mln_fit* f = new mln_fit();
+  std::unique_ptr<mln_fit> f(new mln_fit());
   f->ctx = ctx; f->n = n_local; f->m = m; f->d = 0; f->full = false;
   f->ldl = pad16(m); f->ldp = pad16(m);
-  auto body = [&]() -> int {
-    DevIn dl;
-    MLN_TRY(dl.init(ctx, L, (size_t)n_local * m));
-    const size_t l_bytes = sizeof(double) * (size_t)n_local * f->ldl;
-    MLN_HIP(ctx, mln_dmalloc((void**)&f->L, l_bytes));
-    MLN_HIP(ctx, hipMemsetAsync(f->L, 0, l_bytes, ctx->stream));
-    MLN_TRY(launch_copy_block(ctx, dl.dev, m, f->L, f->ldl, n_local, m));
-    if (Lp) {
-      DevIn dp;
-      MLN_TRY(dp.init(ctx, Lp, (size_t)m * m));
-      const size_t lp_bytes = sizeof(double) * (size_t)m * f->ldp;
-      MLN_HIP(ctx, mln_dmalloc((void**)&f->Lp, lp_bytes));
-      MLN_HIP(ctx, hipMemsetAsync(f->Lp, 0, lp_bytes, ctx->stream));
-      MLN_TRY(launch_copy_block(ctx, dp.dev, m, f->Lp, f->ldp, m, m));
-      MLN_TRY(triinv_build(ctx, f->Lp, m, f->ldp, true, true, &f->tri));
-    }
-    MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return fit_alloc_workspace(f);
-  };
-  int rc = body();
-  if (rc != MLN_OK) { fit_free(f); return rc; }
-  *out = f;
+  DevIn dl;
+  MLN_TRY(dl.init(ctx, L, (size_t)n_local * m));
+  MLN_TRY(f->L_own.alloc_zeroed(ctx, (size_t)n_local * f->ldl, "L"));
+  f->L = f->L_own;
+  MLN_TRY(launch_copy_block(ctx, dl.dev, m, f->L, f->ldl, n_local, m));
+  if (Lp) {
+    DevIn dp;
+    MLN_TRY(dp.init(ctx, Lp, (size_t)m * m));
+    MLN_TRY(f->Lp.alloc_zeroed(ctx, (size_t)m * f->ldp, "Lp"));
+    MLN_TRY(launch_copy_block(ctx, dp.dev, m, f->Lp, f->ldp, m, m));
+    MLN_TRY(triinv_build(ctx, f->Lp, m, f->ldp, true, true, &f->tri));
+  }
+  MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MLN_TRY(fit_alloc_workspace(f.get()));
+  *out = f.release();
   return MLN_OK;
 }
 
@@ -438,41 +416,36 @@ extern "C" int mln_fit_prepare_from_K(mln_ctx* ctx, const double* Kuu, int64_t n
   if (!Kuu && !Lp_in) { mln_set_error(ctx, "mln_fit_prepare_from_K needs cov(xu, xu) or its factor"); return MLN_ERR_ARG; }
   if (full && ctx->n_ranks > 1) { mln_set_error(ctx, "the full (non-sparse) GP cannot be cell-sharded"); return MLN_ERR_UNSUPPORTED; }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
-  mln_fit* f = new mln_fit();
+  std::unique_ptr<mln_fit> f(new mln_fit());
   f->ctx = ctx; f->n = n_local; f->m = m; f->d = 0; f->full = full;
   f->ldl = pad16(m); f->ldp = pad16(m);
   f->cov.n_leaves = 0; f->cov.n_toks = 0;          // no device program: values only
   f->from_K = true;
   f->kspace = !full && (flags & MLN_FIT_IMPLICIT) != 0;
-  auto body = [&]() -> int {
-    double t0 = now_s();
-    const size_t lp_bytes = sizeof(double) * (size_t)m * f->ldp;
-    MLN_HIP(ctx, mln_dmalloc((void**)&f->Lp, lp_bytes));
-    MLN_HIP(ctx, hipMemsetAsync(f->Lp, 0, lp_bytes, ctx->stream));
-    DevIn dk;
-    MLN_TRY(dk.init(ctx, Lp_in ? Lp_in : Kuu, (size_t)m * m));
-    MLN_TRY(launch_copy_block(ctx, dk.dev, m, f->Lp, f->ldp, m, m));
-    if (!Lp_in) {
-      MLN_TRY(launch_add_diag(ctx, f->Lp, m, f->ldp, jitter));          // decomposition.py:111-114
-      MLN_TRY(dev_cholesky_lower(ctx, f->Lp, m, f->ldp));
-    }
-    MLN_TRY(triinv_build(ctx, f->Lp, m, f->ldp, true, true, &f->tri));
+  double t0 = now_s();
+  MLN_TRY(f->Lp.alloc_zeroed(ctx, (size_t)m * f->ldp, "Lp"));
+  DevIn dk;
+  MLN_TRY(dk.init(ctx, Lp_in ? Lp_in : Kuu, (size_t)m * m));
+  MLN_TRY(launch_copy_block(ctx, dk.dev, m, f->Lp, f->ldp, m, m));
+  if (!Lp_in) {
+    MLN_TRY(launch_add_diag(ctx, f->Lp, m, f->ldp, jitter));          // decomposition.py:111-114
+    MLN_TRY(dev_cholesky_lower(ctx, f->Lp, m, f->ldp));
+  }
+  MLN_TRY(triinv_build(ctx, f->Lp, m, f->ldp, true, true, &f->tri));
+  MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  f->times[1] += now_s() - t0;
+  if (full) {
+    f->L = f->Lp;
+    f->k_rows_done = n_local;
+    MLN_TRY(fit_alloc_workspace(f.get()));
+  } else {
+    const size_t l_count = (size_t)(n_local > 0 ? n_local : 1) * f->ldl;
+    MLN_TRY(f->L_own.alloc(ctx, l_count, "L"));
+    f->L = f->L_own;
+    if (f->ldl != m) MLN_HIP(ctx, hipMemsetAsync(f->L, 0, sizeof(double) * l_count, ctx->stream));      // the pad columns must be zero
     MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    f->times[1] += now_s() - t0;
-    if (full) {
-      f->L = f->Lp;
-      f->k_rows_done = n_local;
-      return fit_alloc_workspace(f);
-    }
-    const size_t l_bytes = sizeof(double) * (size_t)(n_local > 0 ? n_local : 1) * f->ldl;
-    MLN_HIP(ctx, mln_dmalloc((void**)&f->L, l_bytes));
-    if (f->ldl != m) MLN_HIP(ctx, hipMemsetAsync(f->L, 0, l_bytes, ctx->stream));      // the pad columns must be zero
-    MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return MLN_OK;
-  };
-  int rc = body();
-  if (rc != MLN_OK) { fit_free(f); return rc; }
-  *out = f;
+  }
+  *out = f.release();
   return MLN_OK;
 }
 
@@ -515,20 +488,19 @@ extern "C" int mln_fit_gram_eigh(mln_fit* f, double* w, int32_t* n_sweeps) {
   mln_ctx* ctx = f->ctx;
   MLN_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t m = f->m, ld = f->ldl;
-  double* G = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&G, sizeof(double) * (size_t)m * ld));
+  DevBuf<double> G;
+  MLN_TRY(G.alloc(ctx, (size_t)m * ld, "G"));
   // all cells, all ranks; an implicit fit forms Lp^-1 (K^T K) Lp^-T (eigenvalues only are meaningful then:
   // mln_fit_project needs the explicit factor)
   int rc = f->kspace ? fit_gram(f, G, ld, 1) : gram_of(ctx, f->L, f->ldl, f->n, m, 1.0, G, ld);
   if (rc == MLN_OK && !f->eigU) {
-    hipError_t e = mln_dmalloc((void**)&f->eigU, sizeof(double) * (size_t)m * ld);
-    if (e != hipSuccess) rc = mln_hip_fail(ctx, e, "alloc eigenvectors", __FILE__, __LINE__);
+    rc = f->eigU.alloc(ctx, (size_t)m * ld, "eigenvectors");
   }
   std::vector<double> wh((size_t)m);
   int sweeps = 0;
   if (rc == MLN_OK) rc = dev_eigh(ctx, G, m, ld, wh.data(), f->eigU, ld, &sweeps);
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(G);
+  G.reset();
   if (rc != MLN_OK) return rc;
   if (n_sweeps) *n_sweeps = sweeps;
   std::memcpy(w, wh.data(), sizeof(double) * (size_t)m);
@@ -542,8 +514,8 @@ extern "C" int mln_fit_gram_rank(mln_fit* f, double tol, int64_t* rank_out, doub
   mln_ctx* ctx = f->ctx;
   MLN_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t m = f->m, ld = f->ldl;
-  double* G = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&G, sizeof(double) * (size_t)m * ld));
+  DevBuf<double> G;
+  MLN_TRY(G.alloc(ctx, (size_t)m * ld, "G"));
   // With more than 24 cells per landmark the count is taken from the Gram of ~12 m evenly spaced cells (by global index,
   // scaled by the stride; the integer Gram of the preconditioner where the covariance is bounded): the diagnostic only
   // compares the count with 80 % of m (base_model.py:344-355), and the full fp64 Gram is n m^2 flops -- 0.5 s at C3.
@@ -565,7 +537,7 @@ extern "C" int mln_fit_gram_rank(mln_fit* f, double tol, int64_t* rank_out, doub
   if (rc == MLN_OK && !done) rc = dev_sym_rank_above(ctx, G, m, ld, tol * tol, rank_out, &lmax);
   f->rank_path = done ? 1 : 2;
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(G);
+  G.reset();
   if (rc == MLN_OK && sigma_max_out) *sigma_max_out = std::sqrt(std::max(lmax, 0.0));
   return rc;
 }
@@ -578,27 +550,22 @@ extern "C" int mln_fit_project(mln_fit* f, int64_t p, mln_fit** out) {
   if (f->kspace) { mln_set_error(ctx, "project needs the explicit factor (prepare without MLN_FIT_IMPLICIT)"); return MLN_ERR_UNSUPPORTED; }
   if (p < 1 || p > f->m) { mln_set_error(ctx, "project: rank out of range"); return MLN_ERR_SHAPE; }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
-  mln_fit* g = new mln_fit();
+  std::unique_ptr<mln_fit> g(new mln_fit());
   g->ctx = ctx; g->n = f->n; g->m = p; g->d = 0; g->full = false;
   g->ldl = pad16(p); g->ldp = pad16(p);
-  auto body = [&]() -> int {
-    const size_t l_bytes = sizeof(double) * (size_t)(g->n > 0 ? g->n : 1) * g->ldl;
-    MLN_HIP(ctx, mln_dmalloc((void**)&g->L, l_bytes));
-    MLN_HIP(ctx, hipMemsetAsync(g->L, 0, l_bytes, ctx->stream));
-    if (g->n > 0) {
-      GemmArgs a{};
-      a.A = f->L; a.lda = f->ldl; a.ta = 0;                                   // B (n x m)
-      a.B = f->eigU + (f->m - p) * f->ldl; a.ldb = f->ldl; a.tb = 1;          // top-p eigenvectors as rows
-      a.C = g->L; a.ldc = g->ldl;
-      a.M = g->n; a.N = p; a.K = f->m; a.alpha = 1.0; a.beta = 0.0; a.split_k = 1;
-      MLN_TRY(launch_dgemm(ctx, a));
-    }
-    MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return fit_alloc_workspace(g);
-  };
-  int rc = body();
-  if (rc != MLN_OK) { fit_free(g); return rc; }
-  *out = g;
+  MLN_TRY(g->L_own.alloc_zeroed(ctx, (size_t)(g->n > 0 ? g->n : 1) * g->ldl, "L"));
+  g->L = g->L_own;
+  if (g->n > 0) {
+    GemmArgs a{};
+    a.A = f->L; a.lda = f->ldl; a.ta = 0;                                   // B (n x m)
+    a.B = f->eigU + (f->m - p) * f->ldl; a.ldb = f->ldl; a.tb = 1;          // top-p eigenvectors as rows
+    a.C = g->L; a.ldc = g->ldl;
+    a.M = g->n; a.N = p; a.K = f->m; a.alpha = 1.0; a.beta = 0.0; a.split_k = 1;
+    MLN_TRY(launch_dgemm(ctx, a));
+  }
+  MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MLN_TRY(fit_alloc_workspace(g.get()));
+  *out = g.release();
   return MLN_OK;
 }
 
@@ -630,13 +597,13 @@ extern "C" int mln_fit_get_L(mln_fit* f, int64_t row0, int64_t n_rows, double* o
   MLN_TRY(o.init(ctx, out, (size_t)n_rows * f->m));
   if (f->kspace) {  // materialise the requested rows of L = K Lp^-T on demand
     MLN_TRY(fit_ensure_lp(f));
-    double* tmp = nullptr;
-    MLN_HIP(ctx, mln_dmalloc((void**)&tmp, sizeof(double) * (size_t)n_rows * f->ldl));
+    DevBuf<double> tmp;
+    MLN_TRY(tmp.alloc(ctx, (size_t)n_rows * f->ldl, "tmp"));
     int rc = launch_copy_block(ctx, f->L + row0 * f->ldl, f->ldl, tmp, f->ldl, n_rows, f->ldl);
     if (rc == MLN_OK) rc = triinv_solve_right_T(ctx, f->tri, tmp, n_rows, f->ldl);
     if (rc == MLN_OK) rc = launch_copy_block(ctx, tmp, f->ldl, o.dev, f->m, n_rows, f->m);
     if (rc == MLN_OK) rc = o.commit();
-    (void)mln_dfree(tmp);
+    tmp.reset();
     return rc;
   }
   MLN_TRY(launch_copy_block(ctx, f->L + row0 * f->ldl, f->ldl, o.dev, f->m, n_rows, f->m));
@@ -647,9 +614,9 @@ extern "C" int mln_fit_set_likelihood(mln_fit* f, const double* V, const double*
   if (!f || (f->n > 0 && (!V || !Vdr))) return MLN_ERR_ARG;
   mln_ctx* ctx = f->ctx;
   MLN_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = sizeof(double) * (size_t)(f->n > 0 ? f->n : 1);
-  if (!f->V) MLN_HIP(ctx, mln_dmalloc((void**)&f->V, bytes));
-  if (!f->Vdr) MLN_HIP(ctx, mln_dmalloc((void**)&f->Vdr, bytes));
+  const size_t count = (size_t)(f->n > 0 ? f->n : 1);
+  if (!f->V) MLN_TRY(f->V.alloc(ctx, count, "V"));
+  if (!f->Vdr) MLN_TRY(f->Vdr.alloc(ctx, count, "Vdr"));
   if (f->n > 0) {
     MLN_HIP(ctx, hipMemcpyAsync(f->V, V, sizeof(double) * f->n, hipMemcpyDefault, ctx->stream));
     MLN_HIP(ctx, hipMemcpyAsync(f->Vdr, Vdr, sizeof(double) * f->n, hipMemcpyDefault, ctx->stream));

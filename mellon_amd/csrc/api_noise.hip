@@ -62,6 +62,7 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
   // A^T = cov(x, xu) Lp^-T is exactly the factor L of the density path   conditional.py:516-522
   mln_fit* f = nullptr;
   MLN_TRY(mln_fit_prepare(ctx, cov, x, n_local, d, xu, m, jitter, nullptr, 0, &f));
+  std::unique_ptr<mln_fit> fit_owner(f);
   const int64_t ldg = pad16(m), n = n_local;
   // groups of adjacent output columns with one noise level
   std::vector<int64_t> g_begin;
@@ -75,34 +76,33 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
   }
   g_begin.push_back(p);
   const size_t n_groups = g_s2.size();
-  double *G = nullptr, *G0 = nullptr, *R = nullptr, *C = nullptr, *parts = nullptr, *d_scale = nullptr, *d_col = nullptr;
+  DevBuf<double> G, G0, R, C, parts, d_scale, d_col;
   TriInv tb;
   int rc = MLN_OK;
   auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "sparse_solve", __FILE__, __LINE__); };
-  chk(mln_dmalloc((void**)&G, sizeof(double) * (size_t)m * ldg));
-  if (n_groups > 1) chk(mln_dmalloc((void**)&G0, sizeof(double) * (size_t)m * ldg));
-  chk(mln_dmalloc((void**)&C, sizeof(double) * (size_t)m * p));
+  rc = G.alloc(ctx, (size_t)m * ldg, "G");
+  if (rc == MLN_OK && n_groups > 1) rc = G0.alloc(ctx, (size_t)m * ldg, "G0");
+  if (rc == MLN_OK) rc = C.alloc(ctx, (size_t)m * p, "C");
   DevIn dy;
   if (rc == MLN_OK) rc = dy.init(ctx, y, (size_t)n * p);
   // r = y - mu
   if (rc == MLN_OK && n > 0) {
-    chk(mln_dmalloc((void**)&R, sizeof(double) * (size_t)n * p));
+    rc = R.alloc(ctx, (size_t)n * p, "R");
     chk(hipMemcpyAsync(R, dy.dev, sizeof(double) * (size_t)n * p, hipMemcpyDeviceToDevice, ctx->stream));
     if (rc == MLN_OK && mu != 0.0) {
       std::vector<double> ones((size_t)n * p, 1.0);
-      double* d1 = nullptr;
-      chk(mln_dmalloc((void**)&d1, sizeof(double) * ones.size()));
+      DevBuf<double> d1;
+      rc = d1.alloc(ctx, ones.size(), "d1");
       chk(hipMemcpyAsync(d1, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice, ctx->stream));
       if (rc == MLN_OK) rc = launch_axpby(ctx, (int64_t)ones.size(), -mu, d1, 1.0, R);
       (void)hipStreamSynchronize(ctx->stream);
-      if (d1) (void)mln_dfree(d1);
     }
   }
   // per-cell noise: rows of A^T and of r divided by sigma_i, after which the solve is the sigma = 1 one
   if (rc == MLN_OK && kind == MLN_SIGMA_PER_CELL && n > 0) {
     std::vector<double> inv((size_t)n);
     for (int64_t i = 0; i < n; ++i) inv[(size_t)i] = 1.0 / sigmas[i];
-    chk(mln_dmalloc((void**)&d_scale, sizeof(double) * (size_t)n));
+    rc = d_scale.alloc(ctx, (size_t)n, "d_scale");
     chk(hipMemcpyAsync(d_scale, inv.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     if (rc == MLN_OK) rc = launch_scale_rows_cols(ctx, f->L, f->ldl, n, m, d_scale, nullptr);
     if (rc == MLN_OK) rc = launch_scale_rows_cols(ctx, R, p, n, p, d_scale, nullptr);
@@ -116,7 +116,7 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
     if (split < 1) split = 1;
     if (split > 16) split = 16;
     const size_t stride = (size_t)m * p;
-    if (split > 1) chk(mln_dmalloc((void**)&parts, sizeof(double) * stride * split));
+    if (split > 1) rc = parts.alloc(ctx, stride * split, "parts");
     if (rc == MLN_OK) chk(hipMemsetAsync(split > 1 ? parts : C, 0, sizeof(double) * stride * (split > 1 ? split : 1), ctx->stream));
     GemmArgs g{};
     g.A = f->L; g.lda = f->ldl; g.B = R; g.ldb = p; g.C = (split > 1) ? parts : C; g.ldc = p;
@@ -128,7 +128,7 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
     if (rc == MLN_OK && n_groups > 1) {
       std::vector<double> inv((size_t)p);
       for (int64_t j = 0; j < p; ++j) inv[(size_t)j] = 1.0 / (sigmas[j] * sigmas[j]);
-      chk(mln_dmalloc((void**)&d_col, sizeof(double) * (size_t)p));
+      rc = d_col.alloc(ctx, (size_t)p, "d_col");
       chk(hipMemcpyAsync(d_col, inv.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
       if (rc == MLN_OK) rc = launch_scale_rows_cols(ctx, C, p, m, p, nullptr, d_col);
       (void)hipStreamSynchronize(ctx->stream);
@@ -139,12 +139,12 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
     //   (A A^T / s^2 + I)^-1 c = U diag(1 / (lam / s^2 + 1)) U^T c,
     // O(m^3 + m^2 p) instead of one m^3/3 Cholesky per level.  The matrix inverted has eigenvalues >= 1, so the
     // spectral form is as well conditioned as the factorisation it replaces.
-    double *V = nullptr, *T = nullptr, *d_lam = nullptr;
+    DevBuf<double> V, T, d_lam;
     std::vector<double> lam((size_t)m);
     int sweeps = 0;
-    chk(mln_dmalloc((void**)&V, sizeof(double) * (size_t)m * ldg));
-    chk(mln_dmalloc((void**)&T, sizeof(double) * (size_t)m * p));
-    chk(mln_dmalloc((void**)&d_lam, sizeof(double) * (size_t)m));
+    rc = V.alloc(ctx, (size_t)m * ldg, "V");
+    if (rc == MLN_OK) rc = T.alloc(ctx, (size_t)m * p, "T");
+    if (rc == MLN_OK) rc = d_lam.alloc(ctx, (size_t)m, "d_lam");
     if (rc == MLN_OK) rc = dev_eigh(ctx, G0, m, ldg, lam.data(), V, ldg, &sweeps);     // row k of V = eigenvector k
     if (rc == MLN_OK) chk(hipMemcpyAsync(d_lam, lam.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     GemmArgs g{};
@@ -155,14 +155,12 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
       int64_t bx = (p + 255) / 256;
       if (bx > 64) bx = 64;
       hipLaunchKernelGGL(k_resolvent_scale, dim3((unsigned)bx, (unsigned)(m < 65535 ? m : 65535), (unsigned)((m + 65534) / 65535)),
-                         dim3(256), 0, ctx->stream, T, p, m, p, d_lam, d_col);
+                         dim3(256), 0, ctx->stream, T.get(), p, m, p, d_lam.get(), d_col.get());
       chk(hipGetLastError());
     }
     g.A = V; g.B = T; g.C = C; g.ta = 1;
     if (rc == MLN_OK) rc = launch_dgemm(ctx, g);                                      // U (.)
     (void)hipStreamSynchronize(ctx->stream);
-    void* tmp[] = {V, T, d_lam};
-    for (void* q : tmp) if (q) (void)mln_dfree(q);
   } else {
     for (size_t gi = 0; gi < n_groups && rc == MLN_OK; ++gi) {
       const int64_t c0 = g_begin[gi], nc = g_begin[gi + 1] - c0;
@@ -174,7 +172,7 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
       if (rc == MLN_OK) rc = triinv_build(ctx, G, m, ldg, true, true, &tb);
       if (rc == MLN_OK) rc = triinv_solve_left(ctx, tb, C + c0, nc, p);
       if (rc == MLN_OK) rc = triinv_solve_left_T(ctx, tb, C + c0, nc, p);
-      if (gi + 1 < n_groups) { (void)hipStreamSynchronize(ctx->stream); triinv_free(&tb); }
+      if (gi + 1 < n_groups) { (void)hipStreamSynchronize(ctx->stream); tb.reset(); }
     }
   }
   // weights = Lp^-T (.)
@@ -188,9 +186,8 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
     if (rc == MLN_OK) rc = o.commit();
   }
   if (rc == MLN_OK && Cs_out) {
-    double* cs = nullptr;
-    chk(mln_dmalloc((void**)&cs, sizeof(double) * (size_t)m * ldg));
-    if (rc == MLN_OK) chk(hipMemsetAsync(cs, 0, sizeof(double) * (size_t)m * ldg, ctx->stream));
+    DevBuf<double> cs;
+    rc = cs.alloc_zeroed(ctx, (size_t)m * ldg, "cs");
     GemmArgs g{};
     g.A = f->Lp; g.lda = f->ldp; g.B = G; g.ldb = ldg; g.C = cs; g.ldc = ldg;
     g.M = m; g.N = m; g.K = m; g.alpha = 1.0; g.beta = 0.0; g.ta = 0; g.tb = 0; g.split_k = 1;
@@ -200,13 +197,8 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
     if (rc == MLN_OK) rc = launch_copy_block(ctx, cs, ldg, o.dev, m, m, m);
     if (rc == MLN_OK) rc = o.commit();
     (void)hipStreamSynchronize(ctx->stream);
-    if (cs) (void)mln_dfree(cs);
   }
   (void)hipStreamSynchronize(ctx->stream);
-  triinv_free(&tb);
-  void* ptrs[] = {G, G0, R, C, parts, d_scale, d_col};
-  for (void* q : ptrs) if (q) (void)mln_dfree(q);
-  fit_free(f);
   return rc;
 }
 
@@ -253,18 +245,19 @@ extern "C" int mln_landmark_leverage(mln_ctx* ctx, const mln_kernel_desc* cov, c
   MLN_HIP(ctx, hipSetDevice(ctx->device));
   mln_fit* f = nullptr;
   MLN_TRY(mln_fit_prepare(ctx, cov, x, n_local, d, xu, m, jitter, Lk, 0, &f));
+  std::unique_ptr<mln_fit> fit_owner(f);
   const int64_t ldg = pad16(m), n = n_local;
-  double *N = nullptr, *Li = nullptr, *J = nullptr, *V = nullptr, *D = nullptr, *Z = nullptr, *d_theta = nullptr, *d_s2 = nullptr;
+  DevBuf<double> N, Li, J, V, D, Z, d_theta, d_s2;
   int rc = MLN_OK;
   auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "landmark_leverage", __FILE__, __LINE__); };
   const size_t mm = sizeof(double) * (size_t)m * ldg;
-  chk(mln_dmalloc((void**)&N, mm));
-  chk(mln_dmalloc((void**)&Li, mm));
-  chk(mln_dmalloc((void**)&J, mm));
-  chk(mln_dmalloc((void**)&V, mm));
-  chk(mln_dmalloc((void**)&D, sizeof(double) * (size_t)m * p));
-  chk(mln_dmalloc((void**)&d_theta, sizeof(double) * (size_t)m));
-  chk(mln_dmalloc((void**)&d_s2, sizeof(double) * (size_t)p));
+  rc = N.alloc(ctx, (size_t)m * ldg, "N");
+  if (rc == MLN_OK) rc = Li.alloc(ctx, (size_t)m * ldg, "Li");
+  if (rc == MLN_OK) rc = J.alloc(ctx, (size_t)m * ldg, "J");
+  if (rc == MLN_OK) rc = V.alloc(ctx, (size_t)m * ldg, "V");
+  if (rc == MLN_OK) rc = D.alloc(ctx, (size_t)m * p, "D");
+  if (rc == MLN_OK) rc = d_theta.alloc(ctx, (size_t)m, "d_theta");
+  if (rc == MLN_OK) rc = d_s2.alloc(ctx, (size_t)p, "d_s2");
   DevOut o;
   if (rc == MLN_OK && n > 0) rc = o.init(ctx, out, (size_t)n * p);
   // N = L^T L (all cells, all ranks) + jitter Lk^-1 Lk^-T
@@ -297,12 +290,12 @@ extern "C" int mln_landmark_leverage(mln_ctx* ctx, const mln_kernel_desc* cov, c
     int64_t bx = (p + 255) / 256;
     if (bx > 64) bx = 64;
     hipLaunchKernelGGL(k_resolvent_table, dim3((unsigned)bx, (unsigned)(m < 65535 ? m : 65535), (unsigned)((m + 65534) / 65535)),
-                       dim3(256), 0, ctx->stream, D, p, m, p, d_theta, d_s2);
+                       dim3(256), 0, ctx->stream, D.get(), p, m, p, d_theta.get(), d_s2.get());
     chk(hipGetLastError());
   }
   // per chunk of cells: Z = L V^T (coordinates of l_i in the eigenbasis), squared, times the resolvent table
   const int64_t chunk = (n < 32768) ? (n > 0 ? n : 1) : 32768;
-  if (rc == MLN_OK) chk(mln_dmalloc((void**)&Z, sizeof(double) * (size_t)chunk * ldg));
+  if (rc == MLN_OK) rc = Z.alloc(ctx, (size_t)chunk * ldg, "Z");
   for (int64_t r0 = 0; r0 < n && rc == MLN_OK; r0 += chunk) {
     const int64_t rows = (n - r0 < chunk) ? n - r0 : chunk;
     GemmArgs g{};
@@ -313,7 +306,7 @@ extern "C" int mln_landmark_leverage(mln_ctx* ctx, const mln_kernel_desc* cov, c
       const int64_t count = rows * ldg;
       int64_t nb = (count + 255) / 256;
       if (nb > 16384) nb = 16384;
-      hipLaunchKernelGGL(k_square_inplace, dim3((unsigned)nb), dim3(256), 0, ctx->stream, Z, count);
+      hipLaunchKernelGGL(k_square_inplace, dim3((unsigned)nb), dim3(256), 0, ctx->stream, Z.get(), count);
       chk(hipGetLastError());
     }
     GemmArgs h{};
@@ -323,9 +316,6 @@ extern "C" int mln_landmark_leverage(mln_ctx* ctx, const mln_kernel_desc* cov, c
   }
   if (rc == MLN_OK && n > 0) rc = o.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  void* ptrs[] = {N, Li, J, V, D, Z, d_theta, d_s2};
-  for (void* q : ptrs) if (q) (void)mln_dfree(q);
-  fit_free(f);
   return rc;
 }
 
@@ -386,17 +376,17 @@ extern "C" int mln_full_conditional_noise(mln_ctx* ctx, const mln_kernel_desc* c
   if (corrected_r2) MLN_TRY(oC.init(ctx, corrected_r2, (size_t)n * p));
   if (variance_W) MLN_TRY(oV.init(ctx, variance_W, (size_t)n * p));
   const int64_t ld = pad16(n), np_ = n * p;
-  double *K = nullptr, *V = nullptr, *D = nullptr, *T = nullptr, *d_lam = nullptr, *d_s = nullptr, *d_sig2 = nullptr;
+  DevBuf<double> K, V, D, T, d_lam, d_s, d_sig2;
   int rc = MLN_OK;
   auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "full_conditional_noise", __FILE__, __LINE__); };
   const size_t nn = sizeof(double) * (size_t)n * ld;
-  chk(mln_dmalloc((void**)&K, nn));
-  chk(mln_dmalloc((void**)&V, nn));
-  chk(mln_dmalloc((void**)&D, sizeof(double) * (size_t)np_));
-  chk(mln_dmalloc((void**)&T, sizeof(double) * (size_t)np_));
-  chk(mln_dmalloc((void**)&d_lam, sizeof(double) * (size_t)n));
-  chk(mln_dmalloc((void**)&d_s, sizeof(double) * (size_t)p));
-  chk(mln_dmalloc((void**)&d_sig2, sizeof(double) * (size_t)p));
+  rc = K.alloc(ctx, (size_t)n * ld, "K");
+  if (rc == MLN_OK) rc = V.alloc(ctx, (size_t)n * ld, "V");
+  if (rc == MLN_OK) rc = D.alloc(ctx, (size_t)np_, "D");
+  if (rc == MLN_OK) rc = T.alloc(ctx, (size_t)np_, "T");
+  if (rc == MLN_OK) rc = d_lam.alloc(ctx, (size_t)n, "d_lam");
+  if (rc == MLN_OK) rc = d_s.alloc(ctx, (size_t)p, "d_s");
+  if (rc == MLN_OK) rc = d_sig2.alloc(ctx, (size_t)p, "d_sig2");
   if (rc == MLN_OK) chk(hipMemsetAsync(K, 0, nn, ctx->stream));
   if (rc == MLN_OK) rc = launch_kernel_matrix(ctx, dc, dx.dev, n, dx.dev, n, d, K, ld, 0.0);
   std::vector<double> lam((size_t)n), s((size_t)p), sig2((size_t)p);
@@ -420,7 +410,7 @@ extern "C" int mln_full_conditional_noise(mln_ctx* ctx, const mln_kernel_desc* c
     g.M = n; g.N = p; g.K = n; g.alpha = 1.0; g.beta = 0.0; g.ta = 0; g.tb = 0; g.split_k = 1;
     int r = launch_dgemm(ctx, g);
     if (r != MLN_OK) return r;
-    hipLaunchKernelGGL(k_mul_inplace, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, T, D, np_);
+    hipLaunchKernelGGL(k_mul_inplace, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, T.get(), D.get(), np_);
     g.B = T; g.C = out; g.ta = 1;
     return launch_dgemm(ctx, g);
   };
@@ -430,35 +420,34 @@ extern "C" int mln_full_conditional_noise(mln_ctx* ctx, const mln_kernel_desc* c
     chk(hipMemcpyAsync(d_sig2, sig2.data(), sizeof(double) * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
     int64_t bx = (p + 255) / 256;
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(k_resolvent_table, dim3((unsigned)bx, (unsigned)n, 1u), dim3(256), 0, ctx->stream, D, p, n, p, d_lam, d_s);
+    hipLaunchKernelGGL(k_resolvent_table, dim3((unsigned)bx, (unsigned)n, 1u), dim3(256), 0, ctx->stream, D.get(), p, n, p, d_lam.get(), d_s.get());
     chk(hipGetLastError());
   }
   // weights: R = y - mu in oW, then the resolvent
-  double* R = nullptr;
-  chk(mln_dmalloc((void**)&R, sizeof(double) * (size_t)np_));
-  if (rc == MLN_OK) hipLaunchKernelGGL(k_shift, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, R, dy.dev, mu, np_);
+  DevBuf<double> R;
+  if (rc == MLN_OK) rc = R.alloc(ctx, (size_t)np_, "R");
+  if (rc == MLN_OK) hipLaunchKernelGGL(k_shift, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, R.get(), dy.dev, mu, np_);
   if (rc == MLN_OK) rc = resolvent(R, oW.dev);
   if (rc == MLN_OK && leverage) {
     // Q = V o V (in place: V is not needed unsquared again until the variance solve, which re-reads K's eigenvectors
     // from a copy), H = Q^T D, then 1 - sigma^2 H
-    double* Q = nullptr;
-    chk(mln_dmalloc((void**)&Q, nn));
+    DevBuf<double> Q;
+    rc = Q.alloc(ctx, (size_t)n * ld, "Q");
     if (rc == MLN_OK) chk(hipMemcpyAsync(Q, V, nn, hipMemcpyDeviceToDevice, ctx->stream));
-    if (rc == MLN_OK) hipLaunchKernelGGL(k_square_inplace, dim3(grid_1d(n * ld)), dim3(256), 0, ctx->stream, Q, n * ld);
+    if (rc == MLN_OK) hipLaunchKernelGGL(k_square_inplace, dim3(grid_1d(n * ld)), dim3(256), 0, ctx->stream, Q.get(), n * ld);
     GemmArgs g{};
     g.A = Q; g.lda = ld; g.B = D; g.ldb = p; g.C = oH.dev; g.ldc = p;
     g.M = n; g.N = p; g.K = n; g.alpha = 1.0; g.beta = 0.0; g.ta = 1; g.tb = 0; g.split_k = 1;
     if (rc == MLN_OK) rc = launch_dgemm(ctx, g);
-    if (rc == MLN_OK) hipLaunchKernelGGL(k_leverage_finish, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, oH.dev, np_, p, d_sig2);
+    if (rc == MLN_OK) hipLaunchKernelGGL(k_leverage_finish, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, oH.dev, np_, p, d_sig2.get());
     (void)hipStreamSynchronize(ctx->stream);
-    if (Q) (void)mln_dfree(Q);
   }
   if (rc == MLN_OK && corrected_r2) {
     GemmArgs g{};
     g.A = K; g.lda = ld; g.B = oW.dev; g.ldb = p; g.C = R; g.ldc = p;                 // K W (K is symmetric, kept by dev_eigh)
     g.M = n; g.N = p; g.K = n; g.alpha = 1.0; g.beta = 0.0; g.ta = 0; g.tb = 0; g.split_k = 1;
     rc = launch_dgemm(ctx, g);
-    if (rc == MLN_OK) hipLaunchKernelGGL(k_hc3, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, oC.dev, dy.dev, R, mu, oH.dev, np_);
+    if (rc == MLN_OK) hipLaunchKernelGGL(k_hc3, dim3(grid_1d(np_)), dim3(256), 0, ctx->stream, oC.dev, dy.dev, R.get(), mu, oH.dev, np_);
     if (rc == MLN_OK && variance_W) rc = resolvent(oC.dev, oV.dev);                    // variance_mu = 0
   }
   chk(hipGetLastError());
@@ -467,8 +456,6 @@ extern "C" int mln_full_conditional_noise(mln_ctx* ctx, const mln_kernel_desc* c
   if (rc == MLN_OK && corrected_r2) rc = oC.commit();
   if (rc == MLN_OK && variance_W) rc = oV.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  void* ptrs[] = {K, V, D, T, R, d_lam, d_s, d_sig2};
-  for (void* q : ptrs) if (q) (void)mln_dfree(q);
   return rc;
 }
 

@@ -28,8 +28,8 @@ __global__ void k_unpack_symmetric(const double* __restrict__ in, int64_t m, int
 // G (m x m, lower triangle valid on every rank) <- the sum over ranks, both triangles filled
 int allreduce_symmetric_lower(mln_ctx* ctx, double* G, int64_t m, int64_t ldg) {
   const int64_t cnt = m * (m + 1) / 2;
-  double* packed = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&packed, sizeof(double) * (size_t)cnt));
+  DevBuf<double> packed;
+  MLN_TRY(packed.alloc(ctx, (size_t)cnt, "packed"));
   const dim3 grid((unsigned)((m + 255) / 256), (unsigned)m), block(256);
   hipLaunchKernelGGL(k_pack_lower, grid, block, 0, ctx->stream, G, m, ldg, packed);
   int rc = dev_allreduce(ctx, packed, cnt);
@@ -38,7 +38,6 @@ int allreduce_symmetric_lower(mln_ctx* ctx, double* G, int64_t m, int64_t ldg) {
     if (hipGetLastError() != hipSuccess) rc = MLN_ERR_HIP;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(packed);
   return rc;
 }
 
@@ -48,8 +47,8 @@ int gram_of(mln_ctx* ctx, const double* A, int64_t lda, int64_t rows, int64_t m,
   if (split < 1) split = 1;
   if (split > 16 && !quantised) split = 16;
   const size_t stride = (size_t)m * ldg;
-  double* parts = nullptr;
-  if (split > 1) MLN_HIP(ctx, mln_dmalloc((void**)&parts, sizeof(double) * stride * split));
+  DevBuf<double> parts;
+  if (split > 1) MLN_TRY(parts.alloc(ctx, stride * split, "parts"));
   GemmArgs g{};
   g.A = A; g.lda = lda; g.B = A; g.ldb = lda;
   g.C = (split > 1) ? parts : G; g.ldc = ldg;
@@ -64,7 +63,6 @@ int gram_of(mln_ctx* ctx, const double* A, int64_t lda, int64_t rows, int64_t m,
   if (rc == MLN_OK && ctx->n_ranks > 1) rc = allreduce_symmetric_lower(ctx, G, m, ldg);      // half the payload: a Gram is symmetric
   else if (rc == MLN_OK) rc = launch_symmetrize_from_lower(ctx, G, m, ldg);
   (void)hipStreamSynchronize(ctx->stream);
-  if (parts) (void)mln_dfree(parts);
   return rc;
 }
 
@@ -80,9 +78,9 @@ extern "C" int mln_diag_gram_i8(mln_ctx* ctx, const double* A, int64_t rows, int
   MLN_TRY(o.init(ctx, out, (size_t)m * m));
   const int split = gram_i8_splits(rows, m);
   const size_t stride = (size_t)m * m;
-  double *parts = nullptr, *G = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&parts, sizeof(double) * stride * split));
-  MLN_HIP(ctx, mln_dmalloc((void**)&G, sizeof(double) * stride));
+  DevBuf<double> parts, G;
+  MLN_TRY(parts.alloc(ctx, stride * split, "parts"));
+  MLN_TRY(G.alloc(ctx, stride, "G"));
   hipEvent_t e0, e1;
   MLN_HIP(ctx, hipEventCreate(&e0));
   MLN_HIP(ctx, hipEventCreate(&e1));
@@ -103,7 +101,6 @@ extern "C" int mln_diag_gram_i8(mln_ctx* ctx, const double* A, int64_t rows, int
   if (rc == MLN_OK) rc = launch_copy_block(ctx, G, m, o.dev, m, m, m);
   if (rc == MLN_OK) rc = o.commit();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(parts); (void)mln_dfree(G);
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return rc;
 }
@@ -121,9 +118,7 @@ int fit_ensure_kj(mln_fit* f) {
   if (f->Kj) return MLN_OK;
   mln_ctx* ctx = f->ctx;
   if (!f->Lp) { mln_set_error(ctx, "this fit handle holds no Lp"); return MLN_ERR_ARG; }
-  const size_t bytes = sizeof(double) * (size_t)f->m * f->ldp;
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->Kj, bytes));
-  MLN_HIP(ctx, hipMemsetAsync(f->Kj, 0, bytes, ctx->stream));
+  MLN_TRY(f->Kj.alloc_zeroed(ctx, (size_t)f->m * f->ldp, "Kj"));
   GemmArgs g{};
   g.A = f->Lp; g.lda = f->ldp; g.B = f->Lp; g.ldb = f->ldp; g.C = f->Kj; g.ldc = f->ldp;
   g.M = f->m; g.N = f->m; g.K = f->m; g.alpha = 1.0; g.beta = 0.0; g.ta = 0; g.tb = 1; g.lower_only = 1;
@@ -153,19 +148,14 @@ int fit_gram(mln_fit* f, double* G, int64_t ldg, int64_t row_stride, bool whiten
   int rc = gram_of(ctx, Ls, f->ldl * row_stride, rows, f->m, (double)row_stride, G, ldg, quant);   // all-reduced
   if (rc != MLN_OK || !whiten) return rc;
   MLN_TRY(fit_ensure_lp(f));
-  double* T = nullptr;
-  {
-    hipError_t e = mln_dmalloc((void**)&T, sizeof(double) * (size_t)f->m * ldg);
-    if (e == hipSuccess) e = hipMemsetAsync(T, 0, sizeof(double) * (size_t)f->m * ldg, ctx->stream);
-    if (e != hipSuccess) rc = mln_hip_fail(ctx, e, "alloc Gram temp", __FILE__, __LINE__);
-  }
+  DevBuf<double> T;
+  rc = T.alloc_zeroed(ctx, (size_t)f->m * ldg, "Gram temp");
   if (rc == MLN_OK) rc = triinv_solve_left(ctx, f->tri, G, f->m, ldg);          // Lp^-1 S
   if (rc == MLN_OK) rc = launch_transpose(ctx, G, ldg, T, ldg, f->m);           // (Lp^-1 S)^T
   if (rc == MLN_OK) rc = triinv_solve_left(ctx, f->tri, T, f->m, ldg);          // Lp^-1 S Lp^-T (symmetric)
   if (rc == MLN_OK) rc = (hipMemcpyAsync(G, T, sizeof(double) * (size_t)f->m * ldg, hipMemcpyDeviceToDevice,
                                          ctx->stream) == hipSuccess) ? MLN_OK : MLN_ERR_HIP;
   (void)hipStreamSynchronize(ctx->stream);
-  if (T) (void)mln_dfree(T);
   return rc;
 }
 
@@ -189,14 +179,7 @@ int fit_gemvT(mln_fit* f, const double* t_dev, double* rhs_dev) {
 // With row_stride > 1 the Gram is estimated from every row_stride-th cell: any SPD matrix is a valid
 // preconditioner / initial guess for a strictly convex problem, and ~8 m rows already give the same
 // iteration count as all n (measured), at 1/row_stride of the n m^2 flops.
-void fit_drop_precond_operators(mln_fit* f) {
-  (void)hipStreamSynchronize(f->ctx->stream);
-  void* ptrs[] = {f->Cinv, f->P, f->Q1, f->Q2};
-  for (void* p : ptrs) if (p) (void)mln_dfree(p);
-  f->Cinv = nullptr; f->P = nullptr; f->Q1 = nullptr; f->Q2 = nullptr;
-}
-
-// f->C holds the matrix to factor -- explicit mode: the Gram L_s^T L_s (the prior's identity is added here); implicit
+// f->pc.C holds the matrix to factor -- explicit mode: the Gram L_s^T L_s (the prior's identity is added here); implicit
 // mode: M = s K_s^T K_s + Kj, the same Hessian at a = 1 in w-space (w = Lp^-T z), never whitened.
 // Explicit mode: C C^T = that, C^-1, and the stacked per-evaluation operators Q1 = C^-T, Q2 = [C^-1 | C^-1].
 // Implicit mode (round 5): R R^T = M.  C = Lp^-1 R satisfies C C^T = I + Lp^-1 (s K_s^T K_s) Lp^-T -- the matrix rounds
@@ -206,17 +189,17 @@ void fit_drop_precond_operators(mln_fit* f) {
 // so the factor Lp is not even needed before the solve ends (fit_prepare may defer it: it then shares THIS chain of
 // launches, dev_cholesky_lower2).  M -- a sum of a positive semi-definite integer Gram and Kj -- cannot lose positive
 // definiteness to the quantisation of its rows the way the whitened matrix did on heavy-tailed data (round 4).
-//   f->C = R,  f->Cinv = R^-1 (lower),  f->P = R^-T (upper);  Q1, Q2 stay empty.
+//   f->pc.C = R,  f->pc.Cinv = R^-1 (lower),  f->pc.P = R^-T (upper);  Q1, Q2 stay empty.
 int fit_factor_precond(mln_fit* f) {
   mln_ctx* ctx = f->ctx;
   const int64_t m = f->m, ldg = f->ldl;
-  const size_t bytes = sizeof(double) * (size_t)m * ldg;
-  int rc = f->kspace ? MLN_OK : launch_add_diag(ctx, f->C, m, ldg, 1.0);  // Ridge alpha = 1 / the prior's Hessian
+  const size_t count = (size_t)m * ldg;
+  int rc = f->kspace ? MLN_OK : launch_add_diag(ctx, f->pc.C, m, ldg, 1.0);  // Ridge alpha = 1 / the prior's Hessian
   if (rc == MLN_OK && f->kspace && f->lp_pending && !f->lp_failed && f->ldp == ldg) {
     // both factorisations in one chain: its 40 dependent block steps are latency, the second matrix only adds flops
     const double t0 = now_s();
     int bad = 0;
-    rc = dev_cholesky_lower2(ctx, f->C, f->Lp, m, ldg, &bad);
+    rc = dev_cholesky_lower2(ctx, f->pc.C, f->Lp, m, ldg, &bad);
     const int rc_lp = (rc == MLN_ERR_NOT_PD && !(bad & 2)) ? MLN_OK : rc;   // (bit 1 clear: only the preconditioner's matrix failed, Lp is fine)
     if (rc == MLN_OK || rc == MLN_ERR_NOT_PD) {
       const std::string msg = ctx->err;
@@ -225,51 +208,40 @@ int fit_factor_precond(mln_fit* f) {
       if (rc != MLN_OK) mln_set_error(ctx, msg);
     }
   } else if (rc == MLN_OK) {
-    rc = dev_cholesky_lower(ctx, f->C, m, ldg);
+    rc = dev_cholesky_lower(ctx, f->pc.C, m, ldg);
   }
   TriInv t;
-  if (rc == MLN_OK) rc = triinv_build(ctx, f->C, m, ldg, true, false, &t);
-  double* inv = nullptr;                             // the factor's explicit inverse
-  auto zeroed = [&](double** p, const char* what) {
-    hipError_t e = mln_dmalloc((void**)p, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, ctx->stream);
-    if (e != hipSuccess) rc = mln_hip_fail(ctx, e, what, __FILE__, __LINE__);
-  };
-  if (rc == MLN_OK) zeroed(&inv, "alloc factor inverse");
+  if (rc == MLN_OK) rc = triinv_build(ctx, f->pc.C, m, ldg, true, false, &t);
+  DevBuf<double> inv;                                // the factor's explicit inverse
+  if (rc == MLN_OK) rc = inv.alloc_zeroed(ctx, count, "factor inverse");
   if (rc == MLN_OK) rc = launch_add_diag(ctx, inv, m, ldg, 1.0);
   if (rc == MLN_OK) rc = triinv_solve_left(ctx, t, inv, m, ldg, true);   // R^-1 I (lower triangular right-hand side)
   if (rc == MLN_OK && f->kspace) {
-    zeroed(&f->P, "alloc P");
-    if (rc == MLN_OK) rc = launch_transpose(ctx, inv, ldg, f->P, ldg, m);        // P = R^-T
+    rc = f->pc.P.alloc_zeroed(ctx, count, "P");
+    if (rc == MLN_OK) rc = launch_transpose(ctx, inv, ldg, f->pc.P, ldg, m);        // P = R^-T
   } else if (rc == MLN_OK) {   // stacked operators for the per-evaluation row-GEMVs of the explicit factor
     const int64_t ld = ldg;
-    const size_t blk = (size_t)m * ld;
-    hipError_t e = mln_dmalloc((void**)&f->Q1, sizeof(double) * blk);
-    if (e == hipSuccess) e = mln_dmalloc((void**)&f->Q2, sizeof(double) * blk * 2);
-    if (e == hipSuccess) e = hipMemsetAsync(f->Q1, 0, sizeof(double) * blk, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(f->Q2, 0, sizeof(double) * blk * 2, ctx->stream);
-    if (e != hipSuccess) rc = mln_hip_fail(ctx, e, "alloc stacked operators", __FILE__, __LINE__);
-    if (rc == MLN_OK) rc = launch_transpose(ctx, inv, ld, f->Q1, ld, m);                      // C^-T
-    if (rc == MLN_OK) rc = launch_copy_block(ctx, inv, ld, f->Q2, ld * 2, m, ld);             // C^-1
+    rc = f->pc.Q1.alloc_zeroed(ctx, count, "stacked operator Q1");
+    if (rc == MLN_OK) rc = f->pc.Q2.alloc_zeroed(ctx, count * 2, "stacked operator Q2");
+    if (rc == MLN_OK) rc = launch_transpose(ctx, inv, ld, f->pc.Q1, ld, m);                      // C^-T
+    if (rc == MLN_OK) rc = launch_copy_block(ctx, inv, ld, f->pc.Q2, ld * 2, m, ld);             // C^-1
     // g_u = C^-1 (z + L^T(a-1)) = [C^-1 | C^-1] [z ; r] -- a two-segment product
-    if (rc == MLN_OK) rc = launch_copy_block(ctx, inv, ld, f->Q2 + ld, ld * 2, m, ld);
+    if (rc == MLN_OK) rc = launch_copy_block(ctx, inv, ld, f->pc.Q2 + ld, ld * 2, m, ld);
   }
   (void)hipStreamSynchronize(ctx->stream);
-  triinv_free(&t);
-  if (rc == MLN_OK) f->Cinv = inv; else if (inv) (void)mln_dfree(inv);
+  if (rc == MLN_OK) f->pc.Cinv = std::move(inv);
   return rc;
 }
 
 int fit_build_precond(mln_fit* f, int64_t row_stride) {
-  if (f->Cinv) return MLN_OK;
+  if (f->pc.Cinv) return MLN_OK;
   mln_ctx* ctx = f->ctx;
   const int64_t m = f->m, ldg = f->ldl;
-  const size_t bytes = sizeof(double) * (size_t)m * ldg;
   double t0 = now_s();
-  MLN_HIP(ctx, mln_dmalloc((void**)&f->C, bytes));
-  int rc = fit_gram(f, f->C, ldg, row_stride, false);
+  MLN_TRY(f->pc.C.alloc(ctx, (size_t)m * ldg, "C"));   // (a matrix left by a build that failed is released first)
+  int rc = fit_gram(f, f->pc.C, ldg, row_stride, false);
   if (rc == MLN_OK && f->kspace) rc = fit_ensure_kj(f);
-  if (rc == MLN_OK && f->kspace) rc = launch_axpby(ctx, m * ldg, 1.0, f->Kj, 1.0, f->C);      // M = s K_s^T K_s + Kj
+  if (rc == MLN_OK && f->kspace) rc = launch_axpby(ctx, m * ldg, 1.0, f->Kj, 1.0, f->pc.C);      // M = s K_s^T K_s + Kj
   MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   f->times[3] += now_s() - t0;
   double t1 = now_s();
@@ -281,22 +253,11 @@ int fit_build_precond(mln_fit* f, int64_t row_stride) {
 
 // The solver's SECOND preconditioner (precond_rebuild.hip): C C^T = I + sum_i a_i L_i L_i^T estimated from an importance
 // sample of ~rows_per_m * m cells at the point whose rows' f = L z + mu is `f_dev`; replaces C, C^-1, P, Q1, Q2.
-void fit_precond_saved_free(mln_fit* f) {
-  bool any = false;
-  for (double* p : f->saved_precond) any = any || p;
-  if (!any) return;
-  (void)hipStreamSynchronize(f->ctx->stream);
-  for (double*& p : f->saved_precond) { if (p) (void)mln_dfree(p); p = nullptr; }
-}
-
 // the saved (first) preconditioner becomes the current one again; the current one is released
 int fit_precond_revert(mln_fit* f) {
-  if (!f->saved_precond[0] || !f->saved_precond[1]) return MLN_ERR_ARG;
-  fit_drop_precond_operators(f);
-  if (f->C) { (void)mln_dfree(f->C); f->C = nullptr; }
-  f->C = f->saved_precond[0]; f->Cinv = f->saved_precond[1]; f->P = f->saved_precond[2];
-  f->Q1 = f->saved_precond[3]; f->Q2 = f->saved_precond[4];
-  for (double*& p : f->saved_precond) p = nullptr;
+  if (!f->pc_saved.C || !f->pc_saved.Cinv) return MLN_ERR_ARG;
+  (void)hipStreamSynchronize(f->ctx->stream);
+  f->pc = std::move(f->pc_saved);
   return MLN_OK;
 }
 
@@ -305,12 +266,12 @@ int fit_precond_revert(mln_fit* f) {
 // 1 / c) -- the pause came on a plateau far from the optimum, the scaled rows' 23-bit digits would hold only the heaviest
 // cells, and the factor built from them stalled the solve for thousands of passes on tree-shaped data.  outcome 2: the
 // Gram's whitening lost positive definiteness (heavy-tailed data, w_max ~ 1e8: "Covariance not positively definite").
-// On success the FIRST preconditioner is kept in f->saved_precond until the solve ends (solver.h: revert_after).
+// On success the FIRST preconditioner is kept in f->pc_saved until the solve ends (solver.h: revert_after).
 int fit_rebuild_precond(mln_fit* f, const double* f_dev, double rows_per_m, int* outcome, double cap) {
   mln_ctx* ctx = f->ctx;
   const int64_t m = f->m, ldg = f->ldl;
   *outcome = 0;
-  RebuildSelection sel{};
+  RebuildSelection sel;
   double target = rows_per_m * (double)m;
   // (tools/emulate_rank.py: one process stands for rank 0 of N and sees only its shard -- "global" sums are local there, and
   //  the importance sample would come out N times this rank's real share: 30 000 rows instead of 3 750 at 8 ranks, a Gram
@@ -331,56 +292,49 @@ int fit_rebuild_precond(mln_fit* f, const double* f_dev, double rows_per_m, int*
                                //  positive definiteness to their rounding)
   if (const char* ev = mln_experiment("MELLON_AMD_REBUILD_RANGE")) range_cap = std::atof(ev);
   if (!(sel.w_max * sel.c <= range_cap) || !std::isfinite(sel.sum_a)) {   // (global quantities: the same decision on every rank)
-    rebuild_selection_free(ctx, &sel);
+    (void)hipStreamSynchronize(ctx->stream);
     *outcome = 1;
     return MLN_OK;
   }
-  double* R = nullptr;
-  int rc = MLN_OK;
+  DevBuf<double> R;
   const int64_t rr = sel.rows > 0 ? sel.rows : 1;
-  if (mln_dmalloc((void**)&R, sizeof(double) * (size_t)rr * f->ldl) != hipSuccess) rc = MLN_ERR_HIP;
+  int rc = R.alloc(ctx, (size_t)rr * f->ldl, "R");
   if (rc == MLN_OK) rc = launch_gather_scale_rows(ctx, f->L, f->ldl, sel.idx, sel.scale, sel.rows, R);
   // the current preconditioner steps aside (kept: fallback now, revert later); the new one is built in fresh buffers
-  double* old_set[5] = {f->C, f->Cinv, f->P, f->Q1, f->Q2};
-  f->C = nullptr; f->Cinv = nullptr; f->P = nullptr; f->Q1 = nullptr; f->Q2 = nullptr;
-  if (rc == MLN_OK && mln_dmalloc((void**)&f->C, sizeof(double) * (size_t)m * ldg) != hipSuccess) rc = MLN_ERR_HIP;
+  Precond old = std::move(f->pc);
+  if (rc == MLN_OK) rc = f->pc.C.alloc(ctx, (size_t)m * ldg, "C");
   lap(1, tl);
   if (rc == MLN_OK) {
     // scaled covariances stay in [0, 1]: the integer Gram applies where it did for the first preconditioner
     bool quant = f->kspace && f->cov_bounded01 && m >= 256;
     if (const char* ev = mln_experiment("MELLON_AMD_GRAM_I8")) quant = quant && std::atoi(ev) != 0;
-    rc = gram_of(ctx, R, f->ldl, sel.rows, m, sel.w_max, f->C, ldg, quant);                   // all-reduced
+    rc = gram_of(ctx, R, f->ldl, sel.rows, m, sel.w_max, f->pc.C, ldg, quant);                   // all-reduced
     // (The integer Gram is that of the rows ROUNDED to 1 / 8355711; the rounding's own Gram, rows * var * I times w_max
     //  and the whitening's |Lp^-1|^2, is an O(0.1) multiple of K_uu^-1.  Subtracting its expectation was tried: no change
     //  in the pass count at w_max ~ 5e3, and at w_max ~ 1e5 the subtraction itself made the matrix indefinite.)
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (R) (void)mln_dfree(R);
-  rebuild_selection_free(ctx, &sel);
+  R.reset();
+  (void)hipStreamSynchronize(ctx->stream);
+  sel.reset();
   lap(2, tl);
   if (rc == MLN_OK && f->kspace) rc = fit_ensure_kj(f);
-  if (rc == MLN_OK && f->kspace) rc = launch_axpby(ctx, m * ldg, 1.0, f->Kj, 1.0, f->C);       // M' = sum_i a_i K_i K_i^T + Kj
+  if (rc == MLN_OK && f->kspace) rc = launch_axpby(ctx, m * ldg, 1.0, f->Kj, 1.0, f->pc.C);       // M' = sum_i a_i K_i K_i^T + Kj
   lap(3, tl);
   if (rc == MLN_OK) rc = fit_factor_precond(f);
   lap(4, tl);
   if (tr_on) fprintf(stderr, "[trace] rebuild ms: select %.2f, gather %.2f, gram %.2f, + Kj %.2f, factor+inverses+stacks %.2f (rc %d)\n",
                      1e3 * tt[0], 1e3 * tt[1], 1e3 * tt[2], 1e3 * tt[3], 1e3 * tt[4], rc);
-  if (rc == MLN_ERR_NOT_PD) {
-    // (the factorisation's verdict is a function of all-reduced numbers: every rank lands here together)
-    fit_drop_precond_operators(f);
-    if (f->C) { (void)hipStreamSynchronize(ctx->stream); (void)mln_dfree(f->C); }
-    f->C = old_set[0]; f->Cinv = old_set[1]; f->P = old_set[2]; f->Q1 = old_set[3]; f->Q2 = old_set[4];
+  if (rc != MLN_OK) {                        // the old set goes back: the handle stays consistent
+    (void)hipStreamSynchronize(ctx->stream);
+    f->pc = std::move(old);
+    // (the factorisation's verdict is a function of all-reduced numbers: every rank lands here together); else a real failure
+    if (rc != MLN_ERR_NOT_PD) return rc;
     *outcome = 2;
     return MLN_OK;
   }
-  if (rc != MLN_OK) {                        // a real failure: leave the handle consistent (old set back), report it
-    fit_drop_precond_operators(f);
-    if (f->C) { (void)hipStreamSynchronize(ctx->stream); (void)mln_dfree(f->C); }
-    f->C = old_set[0]; f->Cinv = old_set[1]; f->P = old_set[2]; f->Q1 = old_set[3]; f->Q2 = old_set[4];
-    return rc;
-  }
-  fit_precond_saved_free(f);
-  for (int i = 0; i < 5; ++i) f->saved_precond[i] = old_set[i];
+  if (f->pc_saved.C) (void)hipStreamSynchronize(ctx->stream);
+  f->pc_saved = std::move(old);
   return MLN_OK;
 }
 
@@ -417,11 +371,11 @@ extern "C" int mln_precond_build(mln_fit* f, int64_t row_stride) {
   if (!f) return MLN_ERR_ARG;
   MLN_HIP(f->ctx, hipSetDevice(f->ctx->device));
   if (row_stride < 1) row_stride = 1;
-  if (f->Cinv && f->precond_stride != row_stride) {
+  if (f->pc.Cinv && f->precond_stride != row_stride) {
     // an explicit request for a DIFFERENT sample (e.g. the reference's exact Ridge, stride 1, after a sampled
     // preconditioner had been built): drop the factor and build the one asked for
-    fit_drop_precond_operators(f);
-    if (f->C) { (void)mln_dfree(f->C); f->C = nullptr; }
+    (void)hipStreamSynchronize(f->ctx->stream);
+    f->pc = Precond();
     f->precond_stride = 0;
   }
   return fit_build_precond(f, row_stride);
@@ -457,17 +411,17 @@ extern "C" int mln_ridge_init(mln_fit* f, const double* target, double* z0) {
     MLN_TRY(launch_reduce_obj(ctx, a, f->d_out));
     MLN_TRY(dev_allreduce(ctx, f->d_out, 1 + f->m));
     // u0 = R^-1 (s K_s^T t) ;  w0 = R^-T u0 ;  z0 = Lp^T w0
-    MLN_TRY(fit_small_gemv(f, f->Cinv, 0, f->d_out + 1, f->d_gu));
-    MLN_TRY(fit_small_gemv(f, f->P, 0, f->d_gu, f->d_w));
+    MLN_TRY(fit_small_gemv(f, f->pc.Cinv, 0, f->d_out + 1, f->d_gu));
+    MLN_TRY(fit_small_gemv(f, f->pc.P, 0, f->d_gu, f->d_w));
     MLN_TRY(fit_ensure_lp(f, false));
     MLN_TRY(fit_small_gemv(f, f->Lp, 1, f->d_w, f->d_z));
   } else {
     MLN_TRY(launch_objective(ctx, a));
     MLN_TRY(launch_reduce_obj(ctx, a, f->d_out));
     MLN_TRY(dev_allreduce(ctx, f->d_out, 1 + f->m));
-    MLN_TRY(fit_small_gemv(f, f->Cinv, 0, f->d_out + 1, f->d_gu));
+    MLN_TRY(fit_small_gemv(f, f->pc.Cinv, 0, f->d_out + 1, f->d_gu));
   }
-  if (!f->kspace) MLN_TRY(fit_small_gemv(f, f->Cinv, 1, f->d_gu, f->d_z));       // z0 = C^-T (.)   [d_gu plays the role of u0]
+  if (!f->kspace) MLN_TRY(fit_small_gemv(f, f->pc.Cinv, 1, f->d_gu, f->d_z));       // z0 = C^-T (.)   [d_gu plays the role of u0]
   MLN_TRY(fit_cache_pair_from_u(f, f->d_gu));
   MLN_HIP(ctx, hipMemcpyAsync(z0, f->d_z, sizeof(double) * f->m, hipMemcpyDefault, ctx->stream));
   MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -487,18 +441,18 @@ extern "C" int mln_precond_apply(mln_fit* f, int32_t mode, const double* in, dou
     MLN_TRY(fit_ensure_lp(f));
     if (mode == 0) {
       MLN_TRY(fit_w_from_z(f, f->d_u, f->d_w, is_device_ptr(in) ? nullptr : in));
-      MLN_TRY(fit_small_gemv(f, f->C, 1, f->d_w, f->d_gu));
+      MLN_TRY(fit_small_gemv(f, f->pc.C, 1, f->d_w, f->d_gu));
     } else if (mode == 1) {
-      MLN_TRY(fit_small_gemv(f, f->P, 0, f->d_u, f->d_w));
+      MLN_TRY(fit_small_gemv(f, f->pc.P, 0, f->d_u, f->d_w));
       MLN_TRY(fit_small_gemv(f, f->Lp, 1, f->d_w, f->d_gu));
     } else {
       MLN_TRY(fit_small_gemv(f, f->Lp, 0, f->d_u, f->d_w));
-      MLN_TRY(fit_small_gemv(f, f->Cinv, 0, f->d_w, f->d_gu));
+      MLN_TRY(fit_small_gemv(f, f->pc.Cinv, 0, f->d_w, f->d_gu));
     }
   }
-  else if (mode == 0) MLN_TRY(fit_small_gemv(f, f->C, 1, f->d_u, f->d_gu));     // u = C^T z
-  else if (mode == 1) MLN_TRY(fit_small_gemv(f, f->Cinv, 1, f->d_u, f->d_gu));  // z = C^-T u
-  else if (mode == 2) MLN_TRY(fit_small_gemv(f, f->Cinv, 0, f->d_u, f->d_gu));  // g_u = C^-1 g_z
+  else if (mode == 0) MLN_TRY(fit_small_gemv(f, f->pc.C, 1, f->d_u, f->d_gu));     // u = C^T z
+  else if (mode == 1) MLN_TRY(fit_small_gemv(f, f->pc.Cinv, 1, f->d_u, f->d_gu));  // z = C^-T u
+  else if (mode == 2) MLN_TRY(fit_small_gemv(f, f->pc.Cinv, 0, f->d_u, f->d_gu));  // g_u = C^-1 g_z
   else { mln_set_error(ctx, "mln_precond_apply: unknown mode"); return MLN_ERR_ARG; }
   MLN_HIP(ctx, hipMemcpyAsync(out, f->d_gu, sizeof(double) * f->m, hipMemcpyDefault, ctx->stream));
   MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -35,7 +35,7 @@ int fit_cache_pair_from_u(mln_fit* f, const double* u_dev) {
   mln_ctx* ctx = f->ctx;
   f->z_cached.assign((size_t)f->m, 0.0);
   MLN_HIP(ctx, hipMemcpyAsync(f->z_cached.data(), f->d_z, sizeof(double) * f->m, hipMemcpyDeviceToHost, ctx->stream));
-  if (f->kspace) MLN_TRY(fit_small_gemv(f, f->P, 0, u_dev, f->d_w_cached));
+  if (f->kspace) MLN_TRY(fit_small_gemv(f, f->pc.P, 0, u_dev, f->d_w_cached));
   MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MLN_OK;
 }
@@ -128,12 +128,12 @@ int fit_enqueue_eval(mln_fit* f, const double* u_dev, double* gn_dev, bool use32
   const int64_t m = f->m, ld = f->ldl, ld2 = f->ld2;
   if (f->kspace) {
     // w = R^-T u (upper triangular rows), then q = Kj w (full rows; the solver's prior is 1/2 w . q)
-    GemvTri g1{f->P, ld, m, u_dev, f->d_w, nullptr, 1, m, m, 0, 0, gate};
+    GemvTri g1{f->pc.P, ld, m, u_dev, f->d_w, nullptr, 1, m, m, 0, 0, gate};
     MLN_TRY(launch_gemv_tri(ctx, g1));
     GemvTri gk{f->Kj, f->ldp, m, f->d_w, f->d_zr, nullptr, 2, m, m, 0, 0, gate};
     MLN_TRY(launch_gemv_tri(ctx, gk));
   } else {
-    GemvTri g1{f->Q1, ld, m, u_dev, f->d_zr, nullptr, 1, m, m, 0, 0, gate};
+    GemvTri g1{f->pc.Q1, ld, m, u_dev, f->d_zr, nullptr, 1, m, m, 0, 0, gate};
     MLN_TRY(launch_gemv_tri(ctx, g1));                                 // z = C^-T u: upper triangular rows
   }
   ObjArgs a = obj_args(f);
@@ -175,11 +175,11 @@ int fit_enqueue_eval(mln_fit* f, const double* u_dev, double* gn_dev, bool use32
   MLN_TRY(launch_reduce_obj2(ctx, a, f->d_zr + ld2 + m, f->d_zr + ld2));
   MLN_TRY(dev_allreduce(ctx, f->d_zr + ld2, m + 2));
   if (f->kspace) {
-    GemvTri g2{f->Cinv, ld, m, f->d_zr, gn_dev, nullptr, 0, m, m, 0, 0, gate};      // g_u = R^-1 (q + r)
+    GemvTri g2{f->pc.Cinv, ld, m, f->d_zr, gn_dev, nullptr, 0, m, m, 0, 0, gate};      // g_u = R^-1 (q + r)
     g2.xadd = f->d_zr + ld2;
     MLN_TRY(launch_gemv_tri(ctx, g2));
   } else {
-    GemvTri g2{f->Q2, 2 * ld, m, f->d_zr, gn_dev, nullptr, 0, m, m, ld, ld2, gate};
+    GemvTri g2{f->pc.Q2, 2 * ld, m, f->d_zr, gn_dev, nullptr, 0, m, m, ld, ld2, gate};
     MLN_TRY(launch_gemv_tri(ctx, g2));                                 // [C^-1 | C^-1] [z ; r]: lower triangular blocks
   }
   return MLN_OK;
@@ -234,12 +234,11 @@ extern "C" int mln_objective_precond(mln_fit* f, const double* u, double* loss, 
 int fit_solver_alloc(mln_fit* f, int maxcor) {
   mln_ctx* ctx = f->ctx;
   if (f->sv_block && f->sv_maxcor >= maxcor) return MLN_OK;
-  if (f->sv_block) { MLN_HIP(ctx, hipStreamSynchronize(ctx->stream)); MLN_HIP(ctx, mln_dfree(f->sv_block)); f->sv_block = nullptr; }
+  if (f->sv_block) { MLN_HIP(ctx, hipStreamSynchronize(ctx->stream)); f->sv_block.reset(); }
   const size_t ld = (size_t)f->ldl;
   const size_t n_dbl = 6 * ld + 2 * (size_t)maxcor * ld + 2 * 64 + 4 * 512 + (sizeof(SolverState) + 63) / 64 * 8;
-  MLN_HIP(ctx, mln_dmalloc(&f->sv_block, sizeof(double) * n_dbl));
-  MLN_HIP(ctx, hipMemsetAsync(f->sv_block, 0, sizeof(double) * n_dbl, ctx->stream));
-  double* p = (double*)f->sv_block;
+  MLN_TRY(f->sv_block.alloc_zeroed(ctx, n_dbl, "sv_block"));
+  double* p = f->sv_block;
   SolverBuffers& b = f->sv;
   b.u = p; p += ld; b.g = p; p += ld; b.un = p; p += ld; b.gn = p; p += ld; b.d = p; p += ld;
   b.S = p; p += (size_t)maxcor * ld; b.Y = p; p += (size_t)maxcor * ld;
@@ -253,7 +252,7 @@ int fit_solver_alloc(mln_fit* f, int maxcor) {
   b.lik = f->d_zr + f->ld2 + f->m;
   b.over = f->d_zr + f->ld2 + f->m + 1;
   f->sv_maxcor = maxcor;
-  if (!f->h_state) MLN_HIP(ctx, mln_hmalloc((void**)&f->h_state, sizeof(SolverState)));
+  if (!f->h_state) MLN_TRY(f->h_state.alloc(ctx, 1, "h_state"));
   return MLN_OK;
 }
 
@@ -269,7 +268,7 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
     return MLN_ERR_UNSUPPORTED;
   }
   MLN_TRY(fit_build_precond(f, 1));
-  fit_events_borrow(ctx, &f->evs);       // (handed back by fit_free, with the handle)
+  fit_events_borrow(ctx, &f->evs);       // (handed back by ~mln_fit, with the handle)
   mln_solver_opts o = {5000, 10, 30, 1e-13, 1e-7};
   if (opts_in) o = *opts_in;
   if (o.maxcor < 1) o.maxcor = 1;
@@ -278,15 +277,15 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
   const int64_t m = f->m;
   MLN_TRY(fit_solver_alloc(f, o.maxcor));
   for (int b = 0; b < 2; ++b)
-    if (!f->f_keep[b]) MLN_HIP(ctx, mln_dmalloc((void**)&f->f_keep[b], sizeof(double) * (size_t)(f->n > 0 ? f->n : 1)));
+    if (!f->f_keep[b]) MLN_TRY(f->f_keep[b].alloc(ctx, (size_t)(f->n > 0 ? f->n : 1), "f_keep"));
   f->f_final = -1;
   // u0 = C^T z0, identical on every rank (implicit mode: C^T z0 = R^T (Lp^-T z0), api_precond.hip fit_factor_precond)
   MLN_HIP(ctx, hipMemcpyAsync(f->d_u, z0, sizeof(double) * m, hipMemcpyDefault, ctx->stream));
   if (f->kspace) {
     MLN_TRY(fit_w_from_z(f, f->d_u, f->d_w, is_device_ptr(z0) ? nullptr : z0));
-    MLN_TRY(fit_small_gemv(f, f->C, 1, f->d_w, f->d_gu));
+    MLN_TRY(fit_small_gemv(f, f->pc.C, 1, f->d_w, f->d_gu));
   } else {
-    MLN_TRY(fit_small_gemv(f, f->C, 1, f->d_u, f->d_gu));
+    MLN_TRY(fit_small_gemv(f, f->pc.C, 1, f->d_u, f->d_gu));
   }
   MLN_TRY(dev_bcast0(ctx, f->d_gu, m));
   // Mixed precision: while an fp32 copy of the n x m buffer exists, the first passes stream it (half the bytes);
@@ -442,21 +441,20 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
       // ---- second preconditioner at the accepted point (whose rows' f the last accepted fp64 pass left in f_keep) ----
       const double tr0 = now_s(), ex_r0 = f->emu_excluded;
       const SolverState ps = *f->h_state;
-      const bool revert = ps.pause_reason == 2 && f->saved_precond[0] != nullptr;
+      const bool revert = ps.pause_reason == 2 && f->pc_saved.C;
       if (!revert && (ps.pause_reason == 2 || !ps.f_valid)) {
         // (f_valid is a function of the solver's state, identical on every rank; keeping f was settled collectively above)
         // no per-row f to weight the cells with / nothing to go back to: resume with the preconditioner we have
         MLN_TRY(launch_solver_resume(ctx, f->sv, ps.gate_after_pause, 0));
       } else {
-        double *zt = nullptr, *gz = nullptr, *cz = nullptr;
-        MLN_HIP(ctx, mln_dmalloc((void**)&zt, sizeof(double) * 3 * (size_t)f->ldl));
-        gz = zt + f->ldl; cz = gz + f->ldl;
-        MLN_HIP(ctx, hipMemsetAsync(zt, 0, sizeof(double) * 3 * (size_t)f->ldl, ctx->stream));
+        DevBuf<double> zt;
+        MLN_TRY(zt.alloc_zeroed(ctx, 3 * (size_t)f->ldl, "zt"));
+        double *gz = zt + f->ldl, *cz = gz + f->ldl;
         // old variable -> z-space:  z = C^-T u,  g_z = C g_u  (and the surrogate's correction c, a gradient in u, likewise);
-        // implicit mode -> w-space (w = Lp^-T z):  w = P u = R^-T u,  g_w = R g_u   (f->C holds R there, P^T = R^-1)
-        int rc = f->kspace ? fit_small_gemv(f, f->P, 0, f->sv.u, zt) : fit_small_gemv(f, f->Cinv, 1, f->sv.u, zt);
-        if (rc == MLN_OK) rc = fit_small_gemv(f, f->C, 0, f->sv.g, gz);
-        if (rc == MLN_OK && ps.corr) rc = fit_small_gemv(f, f->C, 0, f->sv.c, cz);
+        // implicit mode -> w-space (w = Lp^-T z):  w = P u = R^-T u,  g_w = R g_u   (f->pc.C holds R there, P^T = R^-1)
+        int rc = f->kspace ? fit_small_gemv(f, f->pc.P, 0, f->sv.u, zt) : fit_small_gemv(f, f->pc.Cinv, 1, f->sv.u, zt);
+        if (rc == MLN_OK) rc = fit_small_gemv(f, f->pc.C, 0, f->sv.g, gz);
+        if (rc == MLN_OK && ps.corr) rc = fit_small_gemv(f, f->pc.C, 0, f->sv.c, cz);
         // (The curvature pairs could be carried through the change of variable -- s' = T s, y' = T^-T y with T = C'^T C^-T --
         //  but that measured 1-3 full passes WORSE than a fresh history at C3, five data seeds: the new factor already holds
         //  the curvature the old pairs describe, relative to a metric that is gone.  They are dropped.)
@@ -464,12 +462,12 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
         if (rc == MLN_OK) rc = revert ? fit_precond_revert(f) : fit_rebuild_precond(f, f->f_keep[ps.f_slot], rebuild_rows_per_m * (rebuilds_this_solve > 0 ? 2.0 : 1.0), &outcome, ps.cap);
         if (rc == MLN_OK && outcome == 0) {
           // z-space -> new variable:  u = C^T z,  g_u = C^-1 g_z      (w-space:  u = R^T w,  g_u = R^-1 g_w = P^T g_w)
-          rc = fit_small_gemv(f, f->C, 1, zt, f->sv.u);
-          if (rc == MLN_OK) rc = f->kspace ? fit_small_gemv(f, f->P, 1, gz, f->sv.g) : fit_small_gemv(f, f->Cinv, 0, gz, f->sv.g);
-          if (rc == MLN_OK && ps.corr) rc = f->kspace ? fit_small_gemv(f, f->P, 1, cz, f->sv.c) : fit_small_gemv(f, f->Cinv, 0, cz, f->sv.c);
+          rc = fit_small_gemv(f, f->pc.C, 1, zt, f->sv.u);
+          if (rc == MLN_OK) rc = f->kspace ? fit_small_gemv(f, f->pc.P, 1, gz, f->sv.g) : fit_small_gemv(f, f->pc.Cinv, 0, gz, f->sv.g);
+          if (rc == MLN_OK && ps.corr) rc = f->kspace ? fit_small_gemv(f, f->pc.P, 1, cz, f->sv.c) : fit_small_gemv(f, f->pc.Cinv, 0, cz, f->sv.c);
         }
         (void)hipStreamSynchronize(ctx->stream);
-        (void)mln_dfree(zt);
+        zt.reset();
         MLN_TRY(rc);
         if (outcome == 0) {
           // a rebuilt preconditioner is on trial (solver.h: revert_after); a restored one is not.  A mixed solve whose
@@ -506,7 +504,8 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
     if (batch < 16 && f->h_state->gate == MLN_GATE_F64) batch = std::min(batch, 6);
   }
   const SolverState st = *f->h_state;
-  fit_precond_saved_free(f);
+  if (f->pc_saved.C) (void)hipStreamSynchronize(ctx->stream);
+  f->pc_saved = Precond();
   f->n_start_halvings = st.n_shrink;
   // kernel-time accounting from the per-evaluation events (the pass the solver did not select is a ~2 us no-op)
   std::vector<double> tr;
@@ -537,12 +536,12 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
   // z = C^-T u and w = P u at the accepted point, remembered for transform / predictor weights
   {
     if (f->kspace) {                              // w = R^-T u, z = Lp^T w
-      GemvTri g1{f->P, f->ldl, m, f->sv.u, f->d_w_cached, nullptr, 1, m, m, 0, 0, nullptr};
+      GemvTri g1{f->pc.P, f->ldl, m, f->sv.u, f->d_w_cached, nullptr, 1, m, m, 0, 0, nullptr};
       MLN_TRY(launch_gemv_tri(ctx, g1));
       MLN_TRY(fit_ensure_lp(f, false));
       MLN_TRY(fit_small_gemv(f, f->Lp, 1, f->d_w_cached, f->d_z));
     } else {
-      GemvTri g1{f->Q1, f->ldl, m, f->sv.u, f->d_z, nullptr, 1, m, m, 0, 0, nullptr};
+      GemvTri g1{f->pc.Q1, f->ldl, m, f->sv.u, f->d_z, nullptr, 1, m, m, 0, 0, nullptr};
       MLN_TRY(launch_gemv_tri(ctx, g1));
     }
     f->z_cached.assign((size_t)m, 0.0);
@@ -595,13 +594,13 @@ extern "C" int mln_weights_full(mln_fit* f, const double* y, int64_t p, double m
   MLN_HIP(ctx, hipMemcpyAsync(o.dev, y, sizeof(double) * cnt, hipMemcpyDefault, ctx->stream));
   // r = y - mu ; w = Lp^-T Lp^-1 r                                conditional.py:263-264
   if (mu != 0.0) {
-    double* ones = nullptr;
-    MLN_HIP(ctx, mln_dmalloc((void**)&ones, sizeof(double) * cnt));
+    DevBuf<double> ones;
+    MLN_TRY(ones.alloc(ctx, cnt, "ones"));
     std::vector<double> h((size_t)cnt, 1.0);
     MLN_HIP(ctx, hipMemcpyAsync(ones, h.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
     int rc = launch_axpby(ctx, cnt, -mu, ones, 1.0, o.dev);
     (void)hipStreamSynchronize(ctx->stream);
-    (void)mln_dfree(ones);
+    ones.reset();
     if (rc != MLN_OK) return rc;
   }
   MLN_TRY(triinv_solve_left(ctx, f->tri, o.dev, p, p));

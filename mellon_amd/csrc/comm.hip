@@ -143,19 +143,19 @@ int loop_allreduce(mln_ctx* ctx, double* dev, int64_t count) {
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return loop_fail(ctx, "stream failure before all-reduce");
   g->ptr[ctx->rank] = dev;
   if (!g->barrier()) return loop_fail(ctx, "a peer rank failed");
-  double* tmp = nullptr;
-  if (mln_dmalloc((void**)&tmp, sizeof(double) * (size_t)count) != hipSuccess) return loop_fail(ctx, "out of memory");
+  DevBuf<double> tmp;
+  if (tmp.alloc(ctx, (size_t)count, "all-reduce temporary") != MLN_OK) return loop_fail(ctx, "out of memory");
   LoopPtrs in;
   for (int r = 0; r < g->n; ++r) in.p[r] = g->ptr[r];
   int64_t nb = (count + 255) / 256;
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(k_loop_sum, dim3((unsigned)nb), dim3(256), 0, ctx->stream, in, g->n, tmp, count);
   const bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
-  if (!ok) { (void)mln_dfree(tmp); return loop_fail(ctx, "summation kernel failed"); }
-  if (!g->barrier()) { (void)mln_dfree(tmp); return loop_fail(ctx, "a peer rank failed"); }   // everybody has read every buffer
+  if (!ok) return loop_fail(ctx, "summation kernel failed");
+  if (!g->barrier()) return loop_fail(ctx, "a peer rank failed");   // everybody has read every buffer
   hipError_t e = hipMemcpyAsync(dev, tmp, sizeof(double) * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(tmp);
+  tmp.reset();
   if (e != hipSuccess) return loop_fail(ctx, "copy-back failed");
   return MLN_OK;
 }

@@ -1072,8 +1072,8 @@ int launch_predict_mean1(mln_ctx* ctx, const DevCov& cov, const double* x, int64
 int launch_nn_distances_exact(mln_ctx* ctx, const double* x, int64_t n, const double* y, int64_t m, int d,
                               int64_t self_offset, const int64_t* excl, double* out) {
   if (n == 0) return MLN_OK;
-  double* norms = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&norms, sizeof(double) * (size_t)(n + m)));
+  DevBuf<double> norms;
+  MLN_TRY(norms.alloc(ctx, (size_t)(n + m), "norms"));
   double* xx = norms;
   double* yy = norms + n;
   hipLaunchKernelGGL(k_row_sqnorms_all, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x, n, d, xx);
@@ -1086,7 +1086,6 @@ int launch_nn_distances_exact(mln_ctx* ctx, const double* x, int64_t n, const do
                        xx, yy, self_offset, excl, out);
   hipError_t e = hipGetLastError();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(norms);
   if (e != hipSuccess) return mln_hip_fail(ctx, e, "nn_distances", __FILE__, __LINE__);
   return MLN_OK;
 }
@@ -1143,16 +1142,17 @@ int launch_predict_hessian(mln_ctx* ctx, const DevCov& cov, const double* x, int
       cp_total += m * ld;
       if (ld > ldt_max) ldt_max = ld;
     }
-  double *norms = nullptr, *Q = nullptr, *T = nullptr, *cp = nullptr;
+  double* norms = nullptr;
+  DevBuf<double> Q, T, cp;
   MLN_TRY(mln_scratch(ctx, sizeof(double) * (size_t)L * (size_t)(n + m), (void**)&norms));
   double* xx = norms;
   double* yy = norms + (size_t)L * n;
   MLN_TRY(sqnorms(ctx, cov, x, n, d, xx));
   MLN_TRY(sqnorms(ctx, cov, c, m, d, yy));
   const int64_t slot_stride = chunk * ldq;
-  MLN_HIP(ctx, mln_dmalloc((void**)&Q, sizeof(double) * (size_t)n_slots * slot_stride));
-  MLN_HIP(ctx, mln_dmalloc((void**)&T, sizeof(double) * (size_t)chunk * ldt_max));
-  MLN_HIP(ctx, mln_dmalloc((void**)&cp, sizeof(double) * (size_t)cp_total));
+  MLN_TRY(Q.alloc(ctx, (size_t)n_slots * slot_stride, "Q"));
+  MLN_TRY(T.alloc(ctx, (size_t)chunk * ldt_max, "T"));
+  MLN_TRY(cp.alloc(ctx, (size_t)cp_total, "cp"));
   for (int l = 0; l < L; ++l)
     for (int lp = l; lp < L; ++lp) {
       const int64_t ld = cp_ld[(size_t)l * L + lp];
@@ -1190,7 +1190,6 @@ int launch_predict_hessian(mln_ctx* ctx, const DevCov& cov, const double* x, int
   }
   hipError_t e = hipGetLastError();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(Q); (void)mln_dfree(T); (void)mln_dfree(cp);
   if (rc == MLN_OK && e != hipSuccess) rc = mln_hip_fail(ctx, e, "predict_hessian", __FILE__, __LINE__);
   return rc;
 }
@@ -1204,16 +1203,17 @@ int launch_predict_gradient_gemm_multi(mln_ctx* ctx, const DevCov& cov, const do
   for (int l = 0; l < L; ++l) nd_max = cov.leaves[l].ndims > nd_max ? cov.leaves[l].ndims : nd_max;
   const int64_t ldq = ((m + 15) / 16) * 16, ldc = ((nd_max + 1 + 15) / 16) * 16;
   const int64_t chunk = (n < 32768) ? n : 32768;
-  double *norms = nullptr, *Q = nullptr, *T = nullptr, *cext = nullptr;
+  double* norms = nullptr;
+  DevBuf<double> Q, T, cext;
   MLN_TRY(mln_scratch(ctx, sizeof(double) * (size_t)L * (size_t)(n + m), (void**)&norms));
   double* xx = norms;                        // [L][n]
   double* yy = norms + (size_t)L * n;        // [L][m]
   MLN_TRY(sqnorms(ctx, cov, x, n, d, xx));
   MLN_TRY(sqnorms(ctx, cov, c, m, d, yy));
   const int64_t leaf_stride = chunk * ldq;
-  MLN_HIP(ctx, mln_dmalloc((void**)&Q, sizeof(double) * (size_t)L * leaf_stride));
-  MLN_HIP(ctx, mln_dmalloc((void**)&T, sizeof(double) * (size_t)chunk * ldc));
-  MLN_HIP(ctx, mln_dmalloc((void**)&cext, sizeof(double) * (size_t)L * m * ldc));
+  MLN_TRY(Q.alloc(ctx, (size_t)L * leaf_stride, "Q"));
+  MLN_TRY(T.alloc(ctx, (size_t)chunk * ldc, "T"));
+  MLN_TRY(cext.alloc(ctx, (size_t)L * m * ldc, "cext"));
   int rc = MLN_OK;
   for (int l = 0; l < L; ++l)
     hipLaunchKernelGGL(k_grad_centres_leaf, dim3((unsigned)((m * ldc + 255) / 256)), dim3(256), 0, ctx->stream, cov, l, c,
@@ -1238,7 +1238,6 @@ int launch_predict_gradient_gemm_multi(mln_ctx* ctx, const DevCov& cov, const do
   }
   hipError_t e = hipGetLastError();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(Q); (void)mln_dfree(T); (void)mln_dfree(cext);
   if (rc == MLN_OK && e != hipSuccess) rc = mln_hip_fail(ctx, e, "predict_gradient_gemm_multi", __FILE__, __LINE__);
   return rc;
 }
@@ -1250,15 +1249,16 @@ int launch_predict_gradient_gemm(mln_ctx* ctx, const DevCov& cov, const double* 
   const DevLeaf& lf = cov.leaves[0];
   const int64_t ldq = ((m + 15) / 16) * 16, ldc = ((lf.ndims + 1 + 15) / 16) * 16;
   const int64_t chunk = (n < 32768) ? n : 32768;
-  double *norms = nullptr, *Q = nullptr, *T = nullptr, *cext = nullptr;
+  double* norms = nullptr;
+  DevBuf<double> Q, T, cext;
   MLN_TRY(mln_scratch(ctx, sizeof(double) * (size_t)(n + m), (void**)&norms));
   double* xx = norms;
   double* yy = norms + n;
   MLN_TRY(sqnorms(ctx, cov, x, n, d, xx));
   MLN_TRY(sqnorms(ctx, cov, c, m, d, yy));
-  MLN_HIP(ctx, mln_dmalloc((void**)&Q, sizeof(double) * (size_t)chunk * ldq));
-  MLN_HIP(ctx, mln_dmalloc((void**)&T, sizeof(double) * (size_t)chunk * ldc));
-  MLN_HIP(ctx, mln_dmalloc((void**)&cext, sizeof(double) * (size_t)m * ldc));
+  MLN_TRY(Q.alloc(ctx, (size_t)chunk * ldq, "Q"));
+  MLN_TRY(T.alloc(ctx, (size_t)chunk * ldc, "T"));
+  MLN_TRY(cext.alloc(ctx, (size_t)m * ldc, "cext"));
   int rc = MLN_OK;
   hipLaunchKernelGGL(k_grad_centres, dim3((unsigned)((m * ldc + 255) / 256)), dim3(256), 0, ctx->stream, cov, c, m, d,
                      cext, ldc);
@@ -1278,7 +1278,6 @@ int launch_predict_gradient_gemm(mln_ctx* ctx, const DevCov& cov, const double* 
   }
   hipError_t e = hipGetLastError();
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(Q); (void)mln_dfree(T); (void)mln_dfree(cext);
   if (rc == MLN_OK && e != hipSuccess) rc = mln_hip_fail(ctx, e, "predict_gradient_gemm", __FILE__, __LINE__);
   return rc;
 }

@@ -46,8 +46,8 @@ extern "C" int mln_diag_peak(mln_ctx* ctx, int32_t what, int64_t bytes, double* 
   hipEvent_t e0, e1;
   MLN_HIP(ctx, hipEventCreate(&e0));
   MLN_HIP(ctx, hipEventCreate(&e1));
-  double* out = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&out, 64));
+  DevBuf<double> out;
+  MLN_TRY(out.alloc(ctx, 8, "out"));
   float ms = 0.f;
   if (what == 0 || what == 2 || what == 3) {
     // what = 0: non-trivial operands, 2 waves/SIMD; 2: all-zero operands (DVFS probe); 3: 4 waves/SIMD
@@ -63,27 +63,24 @@ extern "C" int mln_diag_peak(mln_ctx* ctx, int32_t what, int64_t bytes, double* 
     *result = flops / (ms * 1e-3) / 1e12;
   } else {
     if (bytes < (1 << 20)) bytes = 1 << 20;
-    double* buf = nullptr;
-    MLN_HIP(ctx, mln_dmalloc((void**)&buf, (size_t)bytes));
-    MLN_HIP(ctx, hipMemsetAsync(buf, 0, (size_t)bytes, ctx->stream));
+    DevBuf<char> buf;
+    MLN_TRY(buf.alloc_zeroed(ctx, (size_t)bytes, "buf"));
     const int grid = ctx->n_cu * 4;
     if (what == 4) {
-      hipLaunchKernelGGL(k_hbm_write, dim3(grid), dim3(512), 0, ctx->stream, (d2*)buf, bytes / 16, 1.0);
+      hipLaunchKernelGGL(k_hbm_write, dim3(grid), dim3(512), 0, ctx->stream, (d2*)buf.get(), bytes / 16, 1.0);
       MLN_HIP(ctx, hipEventRecord(e0, ctx->stream));
-      hipLaunchKernelGGL(k_hbm_write, dim3(grid), dim3(512), 0, ctx->stream, (d2*)buf, bytes / 16, 2.0);
+      hipLaunchKernelGGL(k_hbm_write, dim3(grid), dim3(512), 0, ctx->stream, (d2*)buf.get(), bytes / 16, 2.0);
       MLN_HIP(ctx, hipEventRecord(e1, ctx->stream));
     } else {
-      hipLaunchKernelGGL(k_hbm_read, dim3(grid), dim3(512), 0, ctx->stream, (const d2*)buf, bytes / 16, out);
+      hipLaunchKernelGGL(k_hbm_read, dim3(grid), dim3(512), 0, ctx->stream, (const d2*)buf.get(), bytes / 16, out);
       MLN_HIP(ctx, hipEventRecord(e0, ctx->stream));
-      hipLaunchKernelGGL(k_hbm_read, dim3(grid), dim3(512), 0, ctx->stream, (const d2*)buf, bytes / 16, out);
+      hipLaunchKernelGGL(k_hbm_read, dim3(grid), dim3(512), 0, ctx->stream, (const d2*)buf.get(), bytes / 16, out);
       MLN_HIP(ctx, hipEventRecord(e1, ctx->stream));
     }
     MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
     MLN_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     *result = (double)bytes / (ms * 1e-3) / 1e9;
-    (void)mln_dfree(buf);
   }
-  (void)mln_dfree(out);
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return MLN_OK;
@@ -99,18 +96,18 @@ extern "C" int mln_diag_dgemm(mln_ctx* ctx, int32_t ta, int32_t tb, int64_t M, i
   const size_t a_bytes = sizeof(double) * (size_t)(ta ? K : M) * lda, b_bytes = sizeof(double) * (size_t)(tb ? N : K) * ldb;
   const int split = split_k > 1 ? split_k : 1;
   const size_t c_bytes = sizeof(double) * (size_t)M * ldc * split;
-  double *A = nullptr, *B = nullptr, *Cm = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&A, a_bytes));
-  MLN_HIP(ctx, mln_dmalloc((void**)&B, b_bytes));
-  MLN_HIP(ctx, mln_dmalloc((void**)&Cm, c_bytes));
+  DevBuf<double> A, B, Cm;
+  MLN_TRY(A.alloc(ctx, a_bytes / sizeof(double), "A"));
+  MLN_TRY(B.alloc(ctx, b_bytes / sizeof(double), "B"));
+  MLN_TRY(Cm.alloc(ctx, c_bytes / sizeof(double), "Cm"));
   // non-trivial data: fill with a repeating host pattern (random-like, avoids the zero-data DVFS bonus)
   std::vector<double> pat(1 << 20);
   unsigned long long s = 88172645463325252ULL;
   for (auto& v : pat) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; v = (double)(s >> 11) / 9007199254740992.0 - 0.5; }
   for (size_t off = 0; off < a_bytes; off += pat.size() * 8)
-    MLN_HIP(ctx, hipMemcpyAsync((char*)A + off, pat.data(), std::min(pat.size() * 8, a_bytes - off), hipMemcpyHostToDevice, ctx->stream));
+    MLN_HIP(ctx, hipMemcpyAsync((char*)A.get() + off, pat.data(), std::min(pat.size() * 8, a_bytes - off), hipMemcpyHostToDevice, ctx->stream));
   for (size_t off = 0; off < b_bytes; off += pat.size() * 8)
-    MLN_HIP(ctx, hipMemcpyAsync((char*)B + off, pat.data(), std::min(pat.size() * 8, b_bytes - off), hipMemcpyHostToDevice, ctx->stream));
+    MLN_HIP(ctx, hipMemcpyAsync((char*)B.get() + off, pat.data(), std::min(pat.size() * 8, b_bytes - off), hipMemcpyHostToDevice, ctx->stream));
   GemmArgs g{};
   g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = Cm; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
   g.alpha = 1.0; g.beta = 0.0; g.ta = ta; g.tb = tb; g.lower_only = lower_only; g.split_k = split;
@@ -126,7 +123,6 @@ extern "C" int mln_diag_dgemm(mln_ctx* ctx, int32_t ta, int32_t tb, int64_t M, i
   float ms = 0.f;
   MLN_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
   *ms_out = ms / reps;
-  (void)mln_dfree(A); (void)mln_dfree(B); (void)mln_dfree(Cm);
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return MLN_OK;
 }
@@ -167,16 +163,16 @@ extern "C" int mln_diag_dgemm_compare(mln_ctx* ctx, int32_t ta, int32_t tb, int6
   const int64_t lda = ((ta ? M : K) + 15) / 16 * 16, ldb = ((tb ? K : N) + 15) / 16 * 16, ldc = (N + 15) / 16 * 16;
   const size_t a_bytes = sizeof(double) * (size_t)(ta ? K : M) * lda, b_bytes = sizeof(double) * (size_t)(tb ? N : K) * ldb;
   const size_t c_count = (size_t)M * ldc;
-  double *A = nullptr, *B = nullptr, *C0 = nullptr, *C1 = nullptr, *res = nullptr;
+  DevBuf<double> A, B, C0, C1, res;
   // any_size == 2 (round 5): the BATCH dimension -- two products on different operands, once as two launches, once as one
   // launch with batch = 2; everything twice as large, kmode / lower_only as given
   const bool batch_mode = any_size == 2;
   const size_t nb = batch_mode ? 2 : 1;
-  MLN_HIP(ctx, mln_dmalloc((void**)&A, a_bytes * nb));
-  MLN_HIP(ctx, mln_dmalloc((void**)&B, b_bytes * nb));
-  MLN_HIP(ctx, mln_dmalloc((void**)&C0, c_count * 8 * nb));
-  MLN_HIP(ctx, mln_dmalloc((void**)&C1, c_count * 8 * nb));
-  MLN_HIP(ctx, mln_dmalloc((void**)&res, 16));
+  MLN_TRY(A.alloc(ctx, a_bytes / sizeof(double) * nb, "A"));
+  MLN_TRY(B.alloc(ctx, b_bytes / sizeof(double) * nb, "B"));
+  MLN_TRY(C0.alloc(ctx, c_count * nb, "C0"));
+  MLN_TRY(C1.alloc(ctx, c_count * nb, "C1"));
+  MLN_TRY(res.alloc(ctx, 2, "res"));
   std::vector<double> pat((1 << 20) + 7);
   unsigned long long s = 88172645463325252ULL;
   for (auto& v : pat) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; v = (double)(s >> 11) / 9007199254740992.0 - 0.5; }
@@ -231,7 +227,6 @@ extern "C" int mln_diag_dgemm_compare(mln_ctx* ctx, int32_t ta, int32_t tb, int6
     if (e != hipSuccess) rc = mln_hip_fail(ctx, e, "dgemm compare", __FILE__, __LINE__);
   }
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(A); (void)mln_dfree(B); (void)mln_dfree(C0); (void)mln_dfree(C1); (void)mln_dfree(res);
   return rc;
 }
 
@@ -253,23 +248,24 @@ extern "C" int mln_diag_overlap(mln_ctx* ctx, int64_t n, int64_t m, int32_t d, i
   DevCov cov;
   MLN_TRY(mln_lower_cov(ctx, &kd, d, &cov));
   const int64_t ld = (m + 15) / 16 * 16;
-  double *X = nullptr, *Xu = nullptr, *K = nullptr, *G = nullptr, *A = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&X, sizeof(double) * n * d));
-  MLN_HIP(ctx, mln_dmalloc((void**)&Xu, sizeof(double) * m * d));
-  MLN_HIP(ctx, mln_dmalloc((void**)&K, sizeof(double) * n * ld));
-  MLN_HIP(ctx, mln_dmalloc((void**)&G, sizeof(double) * m * ld));
-  MLN_HIP(ctx, mln_dmalloc((void**)&A, sizeof(double) * m * ld));
+  DevBuf<double> X, Xu, K, G, A;
+  MLN_TRY(X.alloc(ctx, n * d, "X"));
+  MLN_TRY(Xu.alloc(ctx, m * d, "Xu"));
+  MLN_TRY(K.alloc(ctx, n * ld, "K"));
+  MLN_TRY(G.alloc(ctx, m * ld, "G"));
+  MLN_TRY(A.alloc(ctx, m * ld, "A"));
   std::vector<double> pat((size_t)1 << 20);
   unsigned long long s = 88172645463325252ULL;
   for (auto& v : pat) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; v = 3.0 * ((double)(s >> 11) / 9007199254740992.0 - 0.5); }
   for (size_t off = 0; off < sizeof(double) * (size_t)n * d; off += pat.size() * 8)
-    MLN_HIP(ctx, hipMemcpyAsync((char*)X + off, pat.data(), std::min(pat.size() * 8, sizeof(double) * (size_t)n * d - off), hipMemcpyHostToDevice, ctx->stream));
+    MLN_HIP(ctx, hipMemcpyAsync((char*)X.get() + off, pat.data(), std::min(pat.size() * 8, sizeof(double) * (size_t)n * d - off), hipMemcpyHostToDevice, ctx->stream));
   MLN_HIP(ctx, hipMemcpyAsync(Xu, pat.data() + 777, sizeof(double) * m * d, hipMemcpyHostToDevice, ctx->stream));
   MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  mln_ctx side = *ctx;   // second stream, own status word
-  side.scratch = nullptr; side.scratch_bytes = 0; side.err.clear();
+  mln_ctx side;   // second stream, own scratch and status word
+  side.device = ctx->device; side.n_cu = ctx->n_cu; side.comm = ctx->comm; side.loop = ctx->loop;
+  side.n_ranks = ctx->n_ranks; side.rank = ctx->rank;
   MLN_HIP(ctx, hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking));
-  MLN_HIP(ctx, mln_dmalloc((void**)&side.d_info, 4 * sizeof(int)));
+  MLN_TRY(side.d_info.alloc(ctx, 4, "d_info"));
   auto run_k = [&]() { (void)launch_kernel_matrix(ctx, cov, X, n, Xu, m, d, K, ld, 0.0); (void)hipStreamSynchronize(ctx->stream); };
   auto run_gram = [&](mln_ctx* c) {
     GemmArgs g{};
@@ -290,9 +286,8 @@ extern "C" int mln_diag_overlap(mln_ctx* ctx, int64_t n, int64_t m, int32_t d, i
   t0 = wall_ms(); { std::thread th([&]() { (void)hipSetDevice(ctx->device); run_chol(&side); }); run_k(); th.join(); } out[4] = wall_ms() - t0;
   t0 = wall_ms(); { std::thread th([&]() { (void)hipSetDevice(ctx->device); run_chol(&side); run_gram(&side); }); run_k(); th.join(); } out[5] = wall_ms() - t0;
   (void)hipDeviceSynchronize();
-  if (side.scratch) (void)mln_dfree(side.scratch);
-  (void)mln_dfree(side.d_info);
+  side.scratch.reset();
+  side.d_info.reset();
   (void)hipStreamDestroy(side.stream);
-  for (void* p : {(void*)X, (void*)Xu, (void*)K, (void*)G, (void*)A}) (void)mln_dfree(p);
   return MLN_OK;
 }

@@ -539,17 +539,17 @@ extern "C" int mln_knn(mln_ctx* ctx, const double* x, int64_t n, const double* y
   if (y == x && m == n) dy.dev = dx.dev, dy.ctx = ctx; else MLN_TRY(dy.init(ctx, y, (size_t)m * d));
   MLN_TRY(o.init(ctx, dist, (size_t)n * k));
   int64_t* di = nullptr;
-  DevScratch si(ctx);
+  DevBuf<int64_t> si;
   if (idx) {
     if (is_device_ptr(idx)) di = idx;
-    else { MLN_HIP(ctx, si.alloc(sizeof(int64_t) * (size_t)n * k)); di = reinterpret_cast<int64_t*>(si.p); }
+    else { MLN_TRY(si.alloc(ctx, (size_t)n * k, "neighbour indices")); di = si; }
   }
   KnnArgs a{dx.dev, n, dy.dev, m, d, k, exclude ? 1 : 0, self_offset, o.dev, di};
   hipLaunchKernelGGL(k_knn, dim3((unsigned)((n + KNN_QB - 1) / KNN_QB)), dim3(KNN_WG), 0, ctx->stream, a);
   MLN_HIP(ctx, hipGetLastError());
   if (idx && di != idx)
     MLN_HIP(ctx, hipMemcpyAsync(idx, di, sizeof(int64_t) * (size_t)n * k, hipMemcpyDeviceToHost, ctx->stream));
-  return o.commit();
+  return o.commit();   // (drains the stream: the index copy is idle when it is released)
 }
 
 extern "C" int mln_local_dimensionality(mln_ctx* ctx, const double* x, int64_t n, int32_t d, const int64_t* nbr,
@@ -565,15 +565,15 @@ extern "C" int mln_local_dimensionality(mln_ctx* ctx, const double* x, int64_t n
   MLN_TRY(dx.init(ctx, x, (size_t)n * d));
   MLN_TRY(o.init(ctx, out, (size_t)q));
   const int64_t* dn = nbr;
-  DevScratch sn(ctx);
+  DevBuf<int64_t> sn;
   if (!is_device_ptr(nbr)) {
-    MLN_HIP(ctx, sn.alloc(sizeof(int64_t) * (size_t)q * k));
-    MLN_HIP(ctx, hipMemcpyAsync(sn.p, nbr, sizeof(int64_t) * (size_t)q * k, hipMemcpyHostToDevice, ctx->stream));
-    dn = reinterpret_cast<const int64_t*>(sn.p);
+    MLN_TRY(sn.alloc(ctx, (size_t)q * k, "neighbour indices"));
+    MLN_HIP(ctx, hipMemcpyAsync(sn, nbr, sizeof(int64_t) * (size_t)q * k, hipMemcpyHostToDevice, ctx->stream));
+    dn = sn;
   }
   hipLaunchKernelGGL(k_local_dim, dim3((unsigned)q), dim3(LD_WG), 0, ctx->stream, dx.dev, n, (int)d, dn, (int)k, o.dev);
   MLN_HIP(ctx, hipGetLastError());
-  return o.commit();
+  return o.commit();   // (drains the stream: the index copy is idle when it is released)
 }
 
 static int dim_one_pass_ok(mln_fit* f) {
@@ -592,14 +592,13 @@ extern "C" int mln_fit_set_dim_likelihood(mln_fit* f, const double* ell, int32_t
   MLN_TRY(dim_one_pass_ok(f));
   MLN_HIP(ctx, hipSetDevice(ctx->device));
   const size_t ld = (size_t)f->ldl;
-  if (f->dim_ell && f->dim_k != k) { (void)hipStreamSynchronize(ctx->stream); (void)mln_dfree(f->dim_ell); f->dim_ell = nullptr; }
-  if (!f->dim_ell) MLN_HIP(ctx, mln_dmalloc((void**)&f->dim_ell, sizeof(double) * (size_t)(f->n > 0 ? f->n : 1) * k));
-  if (!f->dim_part) MLN_HIP(ctx, mln_dmalloc((void**)&f->dim_part, sizeof(double) * 4 * ld * (size_t)f->n_wg_cap));
+  if (f->dim_ell && f->dim_k != k) { (void)hipStreamSynchronize(ctx->stream); f->dim_ell.reset(); }
+  if (!f->dim_ell) MLN_TRY(f->dim_ell.alloc(ctx, (size_t)(f->n > 0 ? f->n : 1) * k, "dim_ell"));
+  if (!f->dim_part) MLN_TRY(f->dim_part.alloc(ctx, 4 * ld * (size_t)f->n_wg_cap, "dim_part"));
   if (!f->dim_z) {
-    MLN_HIP(ctx, mln_dmalloc((void**)&f->dim_z, sizeof(double) * 4 * ld));   // z (2 ld) and w (2 ld)
-    MLN_HIP(ctx, hipMemsetAsync(f->dim_z, 0, sizeof(double) * 4 * ld, ctx->stream));
+    MLN_TRY(f->dim_z.alloc_zeroed(ctx, 4 * ld, "dim_z"));   // z (2 ld) and w (2 ld)
   }
-  if (!f->dim_out) MLN_HIP(ctx, mln_dmalloc((void**)&f->dim_out, sizeof(double) * (2 + 4 * ld)));
+  if (!f->dim_out) MLN_TRY(f->dim_out.alloc(ctx, (2 + 4 * ld), "dim_out"));
   if (f->n > 0)
     MLN_HIP(ctx, hipMemcpyAsync(f->dim_ell, ell, sizeof(double) * (size_t)f->n * k, hipMemcpyDefault, ctx->stream));
   MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));

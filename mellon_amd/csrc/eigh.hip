@@ -275,23 +275,18 @@ int dev_eigh(mln_ctx* ctx, const double* A, int64_t m, int64_t lda, double* w_ho
   const int64_t ld = 2 * mp;
   const int nb = (int)(mp / EB);
   const int nbp = (nb % 2 == 0) ? nb : nb + 1;
-  double* Y = nullptr;
-  unsigned* d_rot = nullptr;
-  double* d_w = nullptr;
-  int* d_perm = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&Y, sizeof(double) * (size_t)mp * ld));
-  auto cleanup = [&]() {
+  DevBuf<double> Y, d_w, As;
+  DevBuf<unsigned> d_rot;
+  DevBuf<int> d_perm;
+  MLN_TRY(Y.alloc(ctx, (size_t)mp * ld, "Y"));
+  auto fail = [&](hipError_t e, const char* what) {
     (void)hipStreamSynchronize(ctx->stream);
-    if (Y) (void)mln_dfree(Y);
-    if (d_rot) (void)mln_dfree(d_rot);
-    if (d_w) (void)mln_dfree(d_w);
-    if (d_perm) (void)mln_dfree(d_perm);
+    return mln_hip_fail(ctx, e, what, __FILE__, __LINE__);
   };
-  auto fail = [&](hipError_t e, const char* what) { cleanup(); return mln_hip_fail(ctx, e, what, __FILE__, __LINE__); };
-  hipError_t e = mln_dmalloc((void**)&d_rot, sizeof(unsigned));
-  if (e == hipSuccess) e = mln_dmalloc((void**)&d_w, sizeof(double) * (size_t)mp);
-  if (e == hipSuccess) e = mln_dmalloc((void**)&d_perm, sizeof(int) * (size_t)mp);
-  if (e != hipSuccess) return fail(e, "eigh workspace");
+  MLN_TRY(d_rot.alloc(ctx, 1, "eigh workspace"));
+  MLN_TRY(d_w.alloc(ctx, (size_t)mp, "eigh workspace"));
+  MLN_TRY(d_perm.alloc(ctx, (size_t)mp, "eigh workspace"));
+  hipError_t e;
 
   hipLaunchKernelGGL(k_eigh_init, dim3((unsigned)std::min<int64_t>((mp + 255) / 256, 64), (unsigned)mp), dim3(256), 0,
                      ctx->stream, A, lda, m, Y, ld, mp);
@@ -299,15 +294,12 @@ int dev_eigh(mln_ctx* ctx, const double* A, int64_t m, int64_t lda, double* w_ho
   if (e != hipSuccess) return fail(e, "k_eigh_init");
 
   // |A|_F and the symmetrised copy As = X_0 (the per-sweep refresh X <- V As needs it)
-  double* As = nullptr;
-  e = mln_dmalloc((void**)&As, sizeof(double) * (size_t)mp * mp);
-  if (e != hipSuccess) return fail(e, "eigh workspace");
+  MLN_TRY(As.alloc(ctx, (size_t)mp * mp, "eigh workspace"));
   unsigned* h_rot = nullptr;   // pinned: the per-sweep convergence flag comes back without a staging copy
   e = hipHostMalloc((void**)&h_rot, sizeof(unsigned), hipHostMallocDefault);
-  if (e != hipSuccess) { (void)mln_dfree(As); return fail(e, "eigh workspace"); }
+  if (e != hipSuccess) return fail(e, "eigh workspace");
   auto fail2 = [&](hipError_t err, const char* what) {
     (void)hipStreamSynchronize(ctx->stream);
-    (void)mln_dfree(As);
     (void)hipHostFree(h_rot);
     return fail(err, what);
   };
@@ -320,9 +312,9 @@ int dev_eigh(mln_ctx* ctx, const double* A, int64_t m, int64_t lda, double* w_ho
   double fro2 = 0.0;
   for (double v : ss) fro2 += v;
   if (!(fro2 == fro2) || std::isinf(fro2)) {
-    (void)mln_dfree(As);
+    As.reset();
     (void)hipHostFree(h_rot);
-    cleanup();
+    (void)hipStreamSynchronize(ctx->stream);
     mln_set_error(ctx, "eigh: matrix contains NaN or Inf");
     return MLN_ERR_ARG;
   }
@@ -366,11 +358,11 @@ int dev_eigh(mln_ctx* ctx, const double* A, int64_t m, int64_t lda, double* w_ho
     if (launch_dgemm(ctx, g) != MLN_OK) return fail2(hipGetLastError(), "refresh");
   }
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(As);
+  As.reset();
   (void)hipHostFree(h_rot);
   if (n_sweeps_out) *n_sweeps_out = sweep;
   if (!converged) {
-    cleanup();
+    (void)hipStreamSynchronize(ctx->stream);
     mln_set_error(ctx, "eigh: Jacobi iteration did not converge in 40 sweeps");
     return MLN_ERR_NOCONV;
   }
@@ -390,6 +382,6 @@ int dev_eigh(mln_ctx* ctx, const double* A, int64_t m, int64_t lda, double* w_ho
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // perm is a host vector: finish before it dies
   if (e != hipSuccess) return fail(e, "gather");
-  cleanup();
+  (void)hipStreamSynchronize(ctx->stream);
   return MLN_OK;
 }

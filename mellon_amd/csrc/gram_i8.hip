@@ -288,9 +288,9 @@ int launch_gram_i8(mln_ctx* ctx, const double* K, int64_t ldk, int64_t rows, int
   kchunk = (kchunk + GBK - 1) / GBK * GBK;
   if (kchunk > 32768) { mln_set_error(ctx, "gram_i8: k-chunk exceeds the exact int32 range"); return MLN_ERR_ARG; }
   const int64_t Kp = kchunk * n_splits;
-  int8_t* planes = nullptr;
-  GramTile* d_tiles = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&planes, (size_t)3 * Mp * Kp));
+  DevBuf<int8_t> planes;
+  DevBuf<GramTile> d_tiles;
+  MLN_TRY(planes.alloc(ctx, (size_t)3 * Mp * Kp, "Gram digit planes"));
   // tile order: strips of 8 tile rows, column by column inside a strip -> 32 consecutive tiles share ~12 landmark blocks
   std::vector<GramTile> order;
   order.reserve((size_t)(T * (T + 1) / 2));
@@ -298,10 +298,9 @@ int launch_gram_i8(mln_ctx* ctx, const double* K, int64_t ldk, int64_t rows, int
     for (int64_t j = 0; j < std::min(T, s0 + 8); ++j)
       for (int64_t i = std::max(s0, j); i < std::min(T, s0 + 8); ++i) order.push_back(GramTile{(int)i, (int)j});
   const int n_tiles = (int)order.size();
-  hipError_t e = mln_dmalloc((void**)&d_tiles, sizeof(GramTile) * order.size());
-  if (e != hipSuccess) { (void)mln_dfree(planes); return mln_hip_fail(ctx, e, "alloc Gram tile list", __FILE__, __LINE__); }
+  MLN_TRY(d_tiles.alloc(ctx, order.size(), "Gram tile list"));
   int rc = MLN_OK;
-  e = hipMemcpyAsync(d_tiles, order.data(), sizeof(GramTile) * order.size(), hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = hipMemcpyAsync(d_tiles, order.data(), sizeof(GramTile) * order.size(), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) rc = mln_hip_fail(ctx, e, "upload Gram tile list", __FILE__, __LINE__);
   if (rc == MLN_OK) {
@@ -326,7 +325,5 @@ int launch_gram_i8(mln_ctx* ctx, const double* K, int64_t ldk, int64_t rows, int
     }
   }
   (void)hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(planes);
-  (void)mln_dfree(d_tiles);
   return rc;
 }

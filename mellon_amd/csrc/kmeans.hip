@@ -18,7 +18,6 @@
 
 #include "mln_internal.h"
 
-hipError_t mln_dfree_synced(void* p);   // alloc.hip: release after the caller synchronised the only stream that used p
 #include "rowmin_f16.h"
 #include "mln_options.h"
 
@@ -789,37 +788,36 @@ static int kmeans_level(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int
                         int32_t max_iter, double tol, const double* init, double* centers, int32_t* n_iter_out,
                         double* inertia_out) {
   hipStream_t st = ctx->stream;
-  double *dx = nullptr, *dc = nullptr, *xx = nullptr, *cc = nullptr, *mind = nullptr, *bsum = nullptr, *sums = nullptr,
-         *counts = nullptr, *shift = nullptr;
-  int* label = nullptr;
-  int64_t* pick = nullptr;
-  bool own_x = false;
+  // every buffer here is used on st only and st is drained before the function returns: released without the device-wide wait
+  StreamBuf<double> dx_own, dc, xx, cc, mind, bsum, sums, counts, shift;
+  StreamBuf<int> label;
+  StreamBuf<int64_t> pick;
+  double* dx = const_cast<double*>(x);
   hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, x) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) {
-    dx = const_cast<double*>(x);
-  } else {
+  if (!(hipPointerGetAttributes(&attr, x) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))) {
     (void)hipGetLastError();
-    MLN_HIP(ctx, mln_dmalloc((void**)&dx, sizeof(double) * (size_t)n * d));
-    own_x = true;
-    MLN_HIP(ctx, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st));
+    MLN_TRY(dx_own.alloc(ctx, (size_t)n * d, "dx"));
+    dx = dx_own;
   }
   const int64_t nblk = (n + SBLK - 1) / SBLK, nblk_h = (n + 255) / 256;     // (block sums of the fp64 / the half-precision seeding)
-  MLN_HIP(ctx, mln_dmalloc((void**)&dc, sizeof(double) * (size_t)m * d));
-  MLN_HIP(ctx, mln_dmalloc((void**)&xx, sizeof(double) * (size_t)n));
-  MLN_HIP(ctx, mln_dmalloc((void**)&cc, sizeof(double) * (size_t)m));
-  MLN_HIP(ctx, mln_dmalloc((void**)&mind, sizeof(double) * (size_t)n));
-  MLN_HIP(ctx, mln_dmalloc((void**)&bsum, sizeof(double) * (size_t)nblk_h));
-  MLN_HIP(ctx, mln_dmalloc((void**)&sums, sizeof(double) * (size_t)m * d));
-  MLN_HIP(ctx, mln_dmalloc((void**)&counts, sizeof(double) * (size_t)m));
-  MLN_HIP(ctx, mln_dmalloc((void**)&shift, sizeof(double)));
+  MLN_TRY(dc.alloc(ctx, (size_t)m * d, "dc"));
+  MLN_TRY(xx.alloc(ctx, (size_t)n, "xx"));
+  MLN_TRY(cc.alloc(ctx, (size_t)m, "cc"));
+  MLN_TRY(mind.alloc(ctx, (size_t)n, "mind"));
+  MLN_TRY(bsum.alloc(ctx, (size_t)nblk_h, "bsum"));
+  MLN_TRY(sums.alloc(ctx, (size_t)m * d, "sums"));
+  MLN_TRY(counts.alloc(ctx, (size_t)m, "counts"));
+  MLN_TRY(shift.alloc(ctx, 1, "shift"));
   // fixed-point cluster sums: per-column magnitudes -> power-of-two scales [0, d) and their inverses [d, 2d); sq: |shift|^2 per centre
-  unsigned long long* colmax = nullptr;
-  double *colscale = nullptr, *sq = nullptr;
-  MLN_HIP(ctx, mln_dmalloc((void**)&colmax, sizeof(unsigned long long) * (size_t)(d + 1)));
-  MLN_HIP(ctx, mln_dmalloc((void**)&colscale, sizeof(double) * 2 * (size_t)d));
-  MLN_HIP(ctx, mln_dmalloc((void**)&sq, sizeof(double) * (size_t)(m > d ? m : d)));     // (also the d column variances)
-  MLN_HIP(ctx, mln_dmalloc((void**)&label, sizeof(int) * (size_t)n));
-  MLN_HIP(ctx, mln_dmalloc((void**)&pick, sizeof(int64_t)));
+  StreamBuf<unsigned long long> colmax;
+  StreamBuf<double> colscale, sq;
+  MLN_TRY(colmax.alloc(ctx, (size_t)(d + 1), "colmax"));
+  MLN_TRY(colscale.alloc(ctx, 2 * (size_t)d, "colscale"));
+  MLN_TRY(sq.alloc(ctx, (size_t)(m > d ? m : d), "sq"));     // (also the d column variances)
+  MLN_TRY(label.alloc(ctx, (size_t)n, "label"));
+  MLN_TRY(pick.alloc(ctx, 1, "pick"));
+  // (the upload is enqueued after the allocations: an early return above leaves nothing in flight on st)
+  if (dx_own) MLN_HIP(ctx, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st));
   int rc = MLN_OK;
   auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "kmeans", __FILE__, __LINE__); };
 
@@ -841,23 +839,23 @@ static int kmeans_level(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int
   const bool seeded = init == nullptr;
   const bool km_fp16_seed = !(mln_experiment("MELLON_AMD_KM_FP16") && std::atoi(mln_experiment("MELLON_AMD_KM_FP16")) == 0);
   const bool seed_h = km_fp16_seed && d <= 61 && n * m >= ((int64_t)1 << 24) && m >= 2;
-  void* xsplit = nullptr;
-  double* prep = nullptr;          // centre and scale of the half-precision copies (rowmin_prepare)
+  StreamBuf<char> xsplit;
+  StreamBuf<double> prep;          // centre and scale of the half-precision copies (rowmin_prepare)
   if (d <= 64 && n * m >= ((int64_t)1 << 24) && m >= 2 && rc == MLN_OK) {
-    chk(mln_dmalloc((void**)&prep, sizeof(double) * ROWMIN_PREP_DOUBLES));
+    if (rc == MLN_OK) rc = prep.alloc(ctx, ROWMIN_PREP_DOUBLES, "prep");
     if (rc == MLN_OK) rc = rowmin_prepare(ctx, dx, n, nullptr, 0, d, prep);
   }
-  double* xxs = nullptr;           // squared norms of the centred, scaled cells (the error bound of the fp16 sweep needs them)
-  if (prep && rc == MLN_OK) chk(mln_dmalloc((void**)&xxs, sizeof(double) * (size_t)n));
+  StreamBuf<double> xxs;         // squared norms of the centred, scaled cells (the error bound of the fp16 sweep needs them)
+  if (prep && rc == MLN_OK) rc = xxs.alloc(ctx, (size_t)n, "xxs");
   if (seed_h && rc == MLN_OK) {
-    chk(mln_dmalloc(&xsplit, rowmin_split_bytes(n)));
+    rc = xsplit.alloc(ctx, rowmin_split_bytes(n), "xsplit");
     if (rc == MLN_OK) rc = launch_split_f16(ctx, dx, n, d, xsplit, xxs, nullptr, 1, prep);   // role 1: -2 x (also the Lloyd sweeps' operand)
   }
   if (rc == MLN_OK && seeded) chk(hipMemcpyAsync(dc, dx + cur * d, sizeof(double) * d, hipMemcpyDeviceToDevice, st));
   if (rc == MLN_OK && !seeded) chk(hipMemcpyAsync(dc, init, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToDevice, st));
   for (int64_t j = 0; seeded && j + 1 < m && rc == MLN_OK; ++j) {
     if (seed_h) {
-      hipLaunchKernelGGL((k_seed_update_h<256>), dim3((unsigned)nblk_h), dim3(1024), 0, st, reinterpret_cast<const _Float16*>(xsplit), n, d,
+      hipLaunchKernelGGL((k_seed_update_h<256>), dim3((unsigned)nblk_h), dim3(1024), 0, st, reinterpret_cast<const _Float16*>(xsplit.get()), n, d,
                          -0.5f, dc + j * d, prep, mind, bsum, j == 0 ? 1 : 0);
       hipLaunchKernelGGL((k_seed_select<256>), dim3(1), dim3(256), 0, st, bsum, nblk_h, mind, n, rng.uniform(), dx, d, dc + (j + 1) * d);
     } else {
@@ -891,65 +889,64 @@ static int kmeans_level(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int
   const bool km_fp16 = !(mln_experiment("MELLON_AMD_KM_FP16") && std::atoi(mln_experiment("MELLON_AMD_KM_FP16")) == 0);
   const bool fast_assign = km_fp16 && d <= 64 && n * m >= ((int64_t)1 << 24) && m >= 2;
   const bool km_fold = d <= 61;
-  void* csplit = nullptr;
-  float *ccf = nullptr, *m1f = nullptr;
+  StreamBuf<char> csplit;
+  StreamBuf<float> ccf, m1f;
   if (fast_assign && rc == MLN_OK) {
-    const bool have = xsplit != nullptr;       // (the seeding's copy has role 1: right for the folded product)
-    if (!have) chk(mln_dmalloc(&xsplit, rowmin_split_bytes(n)));
-    chk(mln_dmalloc(&csplit, rowmin_split_bytes(m)));
-    chk(mln_dmalloc((void**)&ccf, sizeof(float) * (size_t)m));
-    chk(mln_dmalloc((void**)&m1f, sizeof(float) * (size_t)n));
+    const bool have = (bool)xsplit;            // (the seeding's copy has role 1: right for the folded product)
+    if (!have) rc = xsplit.alloc(ctx, rowmin_split_bytes(n), "xsplit");
+    if (rc == MLN_OK) rc = csplit.alloc(ctx, rowmin_split_bytes(m), "csplit");
+    if (rc == MLN_OK) rc = ccf.alloc(ctx, (size_t)m, "ccf");
+    if (rc == MLN_OK) rc = m1f.alloc(ctx, (size_t)n, "m1f");
     if (rc == MLN_OK && !have) rc = launch_split_f16(ctx, dx, n, d, xsplit, xxs, nullptr, km_fold ? 1 : 0, prep);
   }
   // With the folded fp16 sweep available the iterations carry distance bounds (see k_km_bounds): sweep 0 searches every
   // cell, later sweeps only the cells whose bounds no longer decide; the sums of the clusters follow the cells that moved.
   const bool km_bounds = fast_assign && km_fold && xxs && !(mln_experiment("MELLON_AMD_KM_BOUNDS") && std::atoi(mln_experiment("MELLON_AMD_KM_BOUNDS")) == 0);
-  double *ub = nullptr, *lb = nullptr, *delta = nullptr, *dstat = nullptr, *yy = nullptr, *ymax = nullptr;
-  float* m2f = nullptr;
-  int *argc = nullptr, *nflag = nullptr, *flagged = nullptr;
+  StreamBuf<double> ub, lb, delta, dstat, yy, ymax;
+  StreamBuf<float> m2f;
+  StreamBuf<int> argc, nflag, flagged;
   if (km_bounds && rc == MLN_OK) {
-    chk(mln_dmalloc((void**)&ub, sizeof(double) * (size_t)n));
-    chk(mln_dmalloc((void**)&lb, sizeof(double) * (size_t)n));
-    chk(mln_dmalloc((void**)&delta, sizeof(double) * (size_t)m));
-    chk(mln_dmalloc((void**)&dstat, sizeof(double) * 4));
-    chk(mln_dmalloc((void**)&yy, sizeof(double) * (size_t)m));
-    chk(mln_dmalloc((void**)&ymax, sizeof(double)));
-    chk(mln_dmalloc((void**)&m2f, sizeof(float) * (size_t)n));
-    chk(mln_dmalloc((void**)&argc, sizeof(int) * (size_t)n));
-    chk(mln_dmalloc((void**)&nflag, sizeof(int)));
-    chk(mln_dmalloc((void**)&flagged, sizeof(int) * (size_t)n));
+    if (rc == MLN_OK) rc = ub.alloc(ctx, (size_t)n, "ub");
+    if (rc == MLN_OK) rc = lb.alloc(ctx, (size_t)n, "lb");
+    if (rc == MLN_OK) rc = delta.alloc(ctx, (size_t)m, "delta");
+    if (rc == MLN_OK) rc = dstat.alloc(ctx, 4, "dstat");
+    if (rc == MLN_OK) rc = yy.alloc(ctx, (size_t)m, "yy");
+    if (rc == MLN_OK) rc = ymax.alloc(ctx, 1, "ymax");
+    if (rc == MLN_OK) rc = m2f.alloc(ctx, (size_t)n, "m2f");
+    if (rc == MLN_OK) rc = argc.alloc(ctx, (size_t)n, "argc");
+    if (rc == MLN_OK) rc = nflag.alloc(ctx, 1, "nflag");
+    if (rc == MLN_OK) rc = flagged.alloc(ctx, (size_t)n, "flagged");
   }
   // Group bounds (see k_km_gather_centres): 1024 to 8192 centres (at most 32 stages).  MELLON_AMD_KM_PRUNE=0 disables.
   const int S = (int)((m + 255) / 256);
   const bool km_prune = km_bounds && m >= 1024 && S <= 32 && n >= 65536 && n <= 2147483647LL &&
                         !(mln_experiment("MELLON_AMD_KM_PRUNE") && std::atoi(mln_experiment("MELLON_AMD_KM_PRUNE")) == 0);
-  int *kstate = nullptr, *wg_count = nullptr, *wg_off = nullptr, *flagged_tmp = nullptr, *cperm = nullptr, *cposd = nullptr, *perm = nullptr,
-      *label_s = nullptr;
-  double *dcp = nullptr, *cum = nullptr, *dxs = nullptr, *ub_s = nullptr, *lb_s = nullptr;
-  float *lbg = nullptr, *smin = nullptr;
-  uint32_t *smask = nullptr, *rowmask = nullptr;
+  StreamBuf<int> kstate, wg_count, wg_off, flagged_tmp, cperm, cposd, perm, label_s;
+  StreamBuf<double> dcp, cum, dxs, ub_s, lb_s;
+  StreamBuf<float> lbg, smin;
+  StreamBuf<uint32_t> smask, rowmask;
   const int nwg = (int)((n + KB_ROWS - 1) / KB_ROWS);
   if (km_bounds && rc == MLN_OK) {
-    chk(mln_dmalloc((void**)&kstate, sizeof(int) * 2));
-    chk(mln_dmalloc((void**)&wg_count, sizeof(int) * (size_t)nwg));
-    chk(mln_dmalloc((void**)&wg_off, sizeof(int) * (size_t)nwg));
-    chk(mln_dmalloc((void**)&flagged_tmp, sizeof(int) * (size_t)nwg * KB_ROWS));
+    if (rc == MLN_OK) rc = kstate.alloc(ctx, 2, "kstate");
+    if (rc == MLN_OK) rc = wg_count.alloc(ctx, (size_t)nwg, "wg_count");
+    if (rc == MLN_OK) rc = wg_off.alloc(ctx, (size_t)nwg, "wg_off");
+    if (rc == MLN_OK) rc = flagged_tmp.alloc(ctx, (size_t)nwg * KB_ROWS, "flagged_tmp");
     if (rc == MLN_OK) chk(hipMemsetAsync(kstate, 0, sizeof(int) * 2, st));
   }
   if (km_prune && rc == MLN_OK) {
-    chk(mln_dmalloc((void**)&cperm, sizeof(int) * (size_t)m));
-    chk(mln_dmalloc((void**)&cposd, sizeof(int) * (size_t)m));
-    chk(mln_dmalloc((void**)&perm, sizeof(int) * (size_t)n));
-    chk(mln_dmalloc((void**)&label_s, sizeof(int) * (size_t)n));
-    chk(mln_dmalloc((void**)&ub_s, sizeof(double) * (size_t)n));
-    chk(mln_dmalloc((void**)&lb_s, sizeof(double) * (size_t)n));
-    chk(mln_dmalloc((void**)&dcp, sizeof(double) * (size_t)m * d));
-    chk(mln_dmalloc((void**)&cum, sizeof(double) * (size_t)S));
-    chk(mln_dmalloc((void**)&dxs, sizeof(double) * (size_t)n * d));
-    chk(mln_dmalloc((void**)&lbg, sizeof(float) * (size_t)n * S));
-    chk(mln_dmalloc((void**)&smin, sizeof(float) * (size_t)n * S));
-    chk(mln_dmalloc((void**)&smask, sizeof(uint32_t) * (size_t)((n + 255) / 256)));
-    chk(mln_dmalloc((void**)&rowmask, sizeof(uint32_t) * (size_t)n));
+    if (rc == MLN_OK) rc = cperm.alloc(ctx, (size_t)m, "cperm");
+    if (rc == MLN_OK) rc = cposd.alloc(ctx, (size_t)m, "cposd");
+    if (rc == MLN_OK) rc = perm.alloc(ctx, (size_t)n, "perm");
+    if (rc == MLN_OK) rc = label_s.alloc(ctx, (size_t)n, "label_s");
+    if (rc == MLN_OK) rc = ub_s.alloc(ctx, (size_t)n, "ub_s");
+    if (rc == MLN_OK) rc = lb_s.alloc(ctx, (size_t)n, "lb_s");
+    if (rc == MLN_OK) rc = dcp.alloc(ctx, (size_t)m * d, "dcp");
+    if (rc == MLN_OK) rc = cum.alloc(ctx, (size_t)S, "cum");
+    if (rc == MLN_OK) rc = dxs.alloc(ctx, (size_t)n * d, "dxs");
+    if (rc == MLN_OK) rc = lbg.alloc(ctx, (size_t)n * S, "lbg");
+    if (rc == MLN_OK) rc = smin.alloc(ctx, (size_t)n * S, "smin");
+    if (rc == MLN_OK) rc = smask.alloc(ctx, (size_t)((n + 255) / 256), "smask");
+    if (rc == MLN_OK) rc = rowmask.alloc(ctx, (size_t)n, "rowmask");
     if (rc == MLN_OK) chk(hipMemsetAsync(cum, 0, sizeof(double) * (size_t)S, st));
   }
   if (km_bounds && rc == MLN_OK && max_iter > 0) {
@@ -1089,11 +1086,6 @@ static int kmeans_level(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int
   }
   if (n_iter_out) *n_iter_out = it;
   (void)hipStreamSynchronize(st);
-  void* ptrs[] = {dc, xx, cc, mind, bsum, sums, counts, shift, label, pick, xsplit, csplit, ccf, m1f, prep, xxs, ub, lb, delta, dstat, yy, ymax,
-                  m2f, argc, nflag, flagged, colmax, colscale, sq, kstate, wg_count, wg_off, flagged_tmp, cperm, cposd, perm, label_s, ub_s,
-                  lb_s, dcp, cum, dxs, lbg, smin, smask, rowmask};
-  for (void* p : ptrs) if (p) (void)mln_dfree_synced(p);      // everything ran on st, synchronised above
-  if (own_x) (void)mln_dfree_synced(dx);
   return rc;
 }
 
@@ -1349,17 +1341,17 @@ static int sklearn_seed(mln_ctx* ctx, const double* dx, int64_t n, int d, int64_
                         int L, double* dc, int64_t* indices) {
   hipStream_t st = ctx->stream;
   const int64_t nblk = (n + SBLK - 1) / SBLK;
-  double *closest = nullptr, *tmp = nullptr, *part = nullptr, *bsum = nullptr, *duni = nullptr, *cb = nullptr;
-  SkState* state = nullptr;
+  DevBuf<double> closest, tmp, part, bsum, duni, cb;
+  DevBuf<SkState> state;
   int rc = MLN_OK;
   auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "kmeans (sklearn seeding)", __FILE__, __LINE__); };
-  chk(mln_dmalloc((void**)&closest, sizeof(double) * (size_t)n));
-  chk(mln_dmalloc((void**)&tmp, sizeof(double) * (size_t)n * (size_t)L));
-  chk(mln_dmalloc((void**)&part, sizeof(double) * (size_t)nblk * SK_LMAX));
-  chk(mln_dmalloc((void**)&bsum, sizeof(double) * (size_t)nblk));
-  chk(mln_dmalloc((void**)&duni, sizeof(double) * (size_t)std::max<int64_t>(1, (m - 1) * L)));
-  chk(mln_dmalloc((void**)&state, sizeof(SkState)));
-  chk(mln_dmalloc((void**)&cb, sizeof(double) * SK_LMAX * 64));
+  rc = closest.alloc(ctx, (size_t)n, "closest");
+  if (rc == MLN_OK) rc = tmp.alloc(ctx, (size_t)n * (size_t)L, "tmp");
+  if (rc == MLN_OK) rc = part.alloc(ctx, (size_t)nblk * SK_LMAX, "part");
+  if (rc == MLN_OK) rc = bsum.alloc(ctx, (size_t)nblk, "bsum");
+  if (rc == MLN_OK) rc = duni.alloc(ctx, (size_t)std::max<int64_t>(1, (m - 1) * L), "duni");
+  if (rc == MLN_OK) rc = state.alloc(ctx, 1, "state");
+  if (rc == MLN_OK) rc = cb.alloc(ctx, SK_LMAX * 64, "cb");
   if (rc == MLN_OK) {
     chk(hipMemsetAsync(state, 0, sizeof(SkState), st));
     if (m > 1) chk(hipMemcpyAsync(duni, uniforms, sizeof(double) * (size_t)((m - 1) * L), hipMemcpyDefault, st));
@@ -1384,8 +1376,6 @@ static int sklearn_seed(mln_ctx* ctx, const double* dx, int64_t n, int d, int64_
     chk(hipMemcpy(&h, state, sizeof(SkState), hipMemcpyDeviceToHost));
     if (rc == MLN_OK && !std::isfinite(h.pot)) { mln_set_error(ctx, "kmeans (sklearn seeding): x contains non-finite values"); rc = MLN_ERR_ARG; }
   }
-  void* ptrs[] = {closest, tmp, part, bsum, duni, state, cb};
-  for (void* p : ptrs) if (p) (void)mln_dfree(p);
   return rc;
 }
 
@@ -1399,26 +1389,21 @@ extern "C" int mln_kmeans_sklearn(mln_ctx* ctx, const double* x, int64_t n, int3
   }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
   const double* dx = x;
-  double* owned = nullptr;
+  DevBuf<double> owned;
   {
     hipPointerAttribute_t attr;
     if (!(hipPointerGetAttributes(&attr, x) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))) {
       (void)hipGetLastError();
-      MLN_HIP(ctx, mln_dmalloc((void**)&owned, sizeof(double) * (size_t)n * d));
+      MLN_TRY(owned.alloc(ctx, (size_t)n * d, "owned"));
       const hipError_t ce = hipMemcpyAsync(owned, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, ctx->stream);
-      if (ce != hipSuccess) { (void)mln_dfree(owned); return mln_hip_fail(ctx, ce, "kmeans (sklearn seeding): upload", __FILE__, __LINE__); }
+      if (ce != hipSuccess) return mln_hip_fail(ctx, ce, "kmeans (sklearn seeding): upload", __FILE__, __LINE__);
       dx = owned;
     }
   }
-  double* dc = nullptr;
-  int64_t* dind = nullptr;
-  int rc = MLN_OK;
-  if (mln_dmalloc((void**)&dc, sizeof(double) * (size_t)m * d) != hipSuccess ||
-      mln_dmalloc((void**)&dind, sizeof(int64_t) * (size_t)m) != hipSuccess) {
-    (void)hipGetLastError();
-    mln_set_error(ctx, "kmeans (sklearn seeding): out of device memory");
-    rc = MLN_ERR_HIP;                    // (falls through to the clean-up below: `owned` may be an n x d upload)
-  }
+  DevBuf<double> dc;
+  DevBuf<int64_t> dind;
+  int rc = dc.alloc(ctx, (size_t)m * d, "kmeans (sklearn seeding): centres");
+  if (rc == MLN_OK) rc = dind.alloc(ctx, (size_t)m, "kmeans (sklearn seeding): indices");
   if (rc == MLN_OK) rc = sklearn_seed(ctx, dx, n, d, m, first_id, uniforms, n_local_trials, dc, dind);
   if (rc == MLN_OK && indices_out && hipMemcpy(indices_out, dind, sizeof(int64_t) * (size_t)m, hipMemcpyDefault) != hipSuccess) rc = MLN_ERR_HIP;
   // Lloyd's sweeps from these centres over ALL cells, to sklearn's stopping rule (max_iter = 0: the seeding alone)
@@ -1428,9 +1413,6 @@ extern "C" int mln_kmeans_sklearn(mln_ctx* ctx, const double* x, int64_t n, int3
     if (n_iter_out) *n_iter_out = 0;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (dc) (void)mln_dfree(dc);
-  if (dind) (void)mln_dfree(dind);
-  if (owned) (void)mln_dfree(owned);
   return rc;
 }
 
@@ -1458,21 +1440,19 @@ extern "C" int mln_kmeans(mln_ctx* ctx, const double* x, int64_t n, int32_t d, i
   hipStream_t st = ctx->stream;
   // the cells on the device once, for both levels
   const double* dx = x;
-  double* owned = nullptr;
+  StreamBuf<double> owned, xs, c0;   // used on st only, drained below
   hipPointerAttribute_t attr;
   if (!(hipPointerGetAttributes(&attr, x) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))) {
     (void)hipGetLastError();
-    MLN_HIP(ctx, mln_dmalloc((void**)&owned, sizeof(double) * (size_t)n * d));
+    MLN_TRY(owned.alloc(ctx, (size_t)n * d, "owned"));
     MLN_HIP(ctx, hipMemcpyAsync(owned, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st));
     dx = owned;
   }
   const int64_t want = std::max<int64_t>(32 * m, n / 8);
   const int64_t stride = std::max<int64_t>(1, n / want);
   const int64_t ns = (n + stride - 1) / stride;
-  double *xs = nullptr, *c0 = nullptr;
-  int rc = MLN_OK;
-  if (mln_dmalloc((void**)&xs, sizeof(double) * (size_t)ns * d) != hipSuccess ||
-      mln_dmalloc((void**)&c0, sizeof(double) * (size_t)m * d) != hipSuccess) rc = MLN_ERR_HIP;
+  int rc = xs.alloc(ctx, (size_t)ns * d, "xs");
+  if (rc == MLN_OK) rc = c0.alloc(ctx, (size_t)m * d, "c0");
   if (rc == MLN_OK && hipMemcpy2DAsync(xs, sizeof(double) * d, dx, sizeof(double) * d * stride, sizeof(double) * d, (size_t)ns,
                                        hipMemcpyDeviceToDevice, st) != hipSuccess) rc = MLN_ERR_HIP;
   int32_t it0 = 0, it1 = 0;
@@ -1480,8 +1460,5 @@ extern "C" int mln_kmeans(mln_ctx* ctx, const double* x, int64_t n, int32_t d, i
   if (rc == MLN_OK) rc = kmeans_level(ctx, dx, n, d, m, seed, max_iter, tol, c0, centers, &it1, inertia_out);
   if (n_iter_out) *n_iter_out = it0 + it1;
   (void)hipStreamSynchronize(st);
-  if (xs) (void)mln_dfree_synced(xs);
-  if (c0) (void)mln_dfree_synced(c0);
-  if (owned) (void)mln_dfree_synced(owned);
   return rc;
 }

@@ -145,8 +145,8 @@ int dev_sym_lambda_max(mln_ctx* ctx, const double* A, int64_t m, int64_t ld, dou
   *lambda_max = 0.0;
   if (m <= 0) { *converged = true; return MLN_OK; }
   const int chunk = 24, max_steps = 480;
-  double* work = nullptr;   // v, vprev, w (m each), alpha[max_steps], beta[max_steps + 1]
-  MLN_HIP(ctx, mln_dmalloc((void**)&work, sizeof(double) * (size_t)(3 * m + 2 * max_steps + 8)));
+  DevBuf<double> work;   // v, vprev, w (m each), alpha[max_steps], beta[max_steps + 1]
+  MLN_TRY(work.alloc(ctx, (size_t)(3 * m + 2 * max_steps + 8), "work"));
   double *v = work, *vprev = work + m, *w = work + 2 * m, *ab = work + 3 * m;
   hipError_t err = hipMemsetAsync(ab, 0, sizeof(double) * (size_t)(2 * max_steps + 8), ctx->stream);
   hipLaunchKernelGGL(k_lz_init, dim3(1), dim3(LZ), 0, ctx->stream, v, vprev, m);
@@ -173,7 +173,7 @@ int dev_sym_lambda_max(mln_ctx* ctx, const double* A, int64_t m, int64_t ld, dou
       e[(size_t)j] = hab[(size_t)(max_steps + j + 1)];
       finite = finite && std::isfinite(e[(size_t)j]);
     }
-    if (!finite) { (void)mln_dfree(work); mln_set_error(ctx, "rank diagnostic: the Gram is not finite"); return MLN_ERR_NOCONV; }
+    if (!finite) { mln_set_error(ctx, "rank diagnostic: the Gram is not finite"); return MLN_ERR_NOCONV; }
     // an exhausted Krylov space (beta = 0: every later alpha is 0) ends the recurrence: the Ritz values so far are exact
     size_t k = (size_t)done;
     for (int j = 0; j < done; ++j)
@@ -188,7 +188,7 @@ int dev_sym_lambda_max(mln_ctx* ctx, const double* A, int64_t m, int64_t ld, dou
     if (broke || done >= m || (prev >= 0.0 && std::fabs(lmax - prev) <= 1e-14 * std::fabs(lmax) && residual_ok)) { *converged = true; break; }
     prev = lmax;
   }
-  (void)mln_dfree(work);
+  work.reset();
   if (err != hipSuccess) return mln_hip_fail(ctx, err, "lanczos", __FILE__, __LINE__);
   *lambda_max = lmax;
   return MLN_OK;
@@ -208,22 +208,12 @@ int dev_sym_rank_above_ldl(mln_ctx* ctx, double* A, int64_t m, int64_t ld, doubl
   if (!(lmax > 0.0)) { *rank = 0; *ok = true; return MLN_OK; }
   const double thr = std::nextafter(tol2 * lmax, INFINITY);
   constexpr int CB = 128;
-  double *Dinv = nullptr, *Ls = nullptr, *Ls2 = nullptr;
-  int* cnt = nullptr;      // [0] negative pivots, [2..3] bits of the smallest |pivot|
-  auto release = [&]() {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (Dinv) (void)mln_dfree(Dinv);
-    if (cnt) (void)mln_dfree(cnt);
-    if (Ls) (void)mln_dfree(Ls);
-    if (Ls2) (void)mln_dfree(Ls2);
-  };
-  {
-    hipError_t ea = mln_dmalloc((void**)&Dinv, sizeof(double) * 2 * CB * CB);
-    if (ea == hipSuccess) ea = mln_dmalloc((void**)&cnt, 16);
-    if (ea == hipSuccess && m > CB) ea = mln_dmalloc((void**)&Ls, sizeof(double) * (size_t)m * (size_t)ld);
-    if (ea == hipSuccess && m > CB) ea = mln_dmalloc((void**)&Ls2, sizeof(double) * (size_t)m * (size_t)ld);
-    if (ea != hipSuccess) { release(); return mln_hip_fail(ctx, ea, "ldl work space", __FILE__, __LINE__); }
-  }
+  DevBuf<double> Dinv, Ls, Ls2;
+  DevBuf<int> cnt;         // [0] negative pivots, [2..3] bits of the smallest |pivot|
+  MLN_TRY(Dinv.alloc(ctx, 2 * CB * CB, "ldl work space"));
+  MLN_TRY(cnt.alloc(ctx, 4, "ldl work space"));
+  if (m > CB) MLN_TRY(Ls.alloc(ctx, (size_t)m * (size_t)ld, "ldl work space"));
+  if (m > CB) MLN_TRY(Ls2.alloc(ctx, (size_t)m * (size_t)ld, "ldl work space"));
   double* DinvS = Dinv + CB * CB;
   unsigned long long* minp = reinterpret_cast<unsigned long long*>(cnt + 2);
   const unsigned long long inf_bits = 0x7ff0000000000000ULL;
@@ -263,7 +253,7 @@ int dev_sym_rank_above_ldl(mln_ctx* ctx, double* A, int64_t m, int64_t ld, doubl
   } else {
     (void)hipStreamSynchronize(ctx->stream);
   }
-  release();
+  (void)hipStreamSynchronize(ctx->stream);
   if (rc != MLN_OK) return rc;
   unsigned long long bits = 0;
   std::memcpy(&bits, hcnt + 2, 8);

@@ -3,15 +3,15 @@
 #include "mln_internal.h"
 
 struct TriInv {
-  double* W = nullptr;   // row-scaled    (forward solves, X Lf^-T)
-  double* W2 = nullptr;  // column-scaled (transposed / backward solves)
+  DevBuf<double> W;   // row-scaled    (forward solves, X Lf^-T)
+  DevBuf<double> W2;  // column-scaled (transposed / backward solves)
   int64_t m = 0, ld = 0;
   const double* Lf = nullptr;  // the factor itself (not owned; must outlive this object)
   int64_t ldf = 0;
+  void reset() { W.reset(); W2.reset(); }
 };
 
 int triinv_build(mln_ctx* ctx, const double* Lf, int64_t m, int64_t ld, bool need_w, bool need_w2, TriInv* out);
-void triinv_free(TriInv* t);
 int triinv_solve_right_T(mln_ctx* ctx, const TriInv& t, double* X, int64_t n, int64_t ldx);  // X <- X Lf^-T
 // `tri_b`: B is itself lower triangular (solve_left) / upper triangular (solve_left_T) with m columns: the result has
 // the same shape and only the columns that can be non-zero in each row block are computed (half the flops).

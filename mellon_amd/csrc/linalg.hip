@@ -222,13 +222,11 @@ static int cholesky_lower_batched(mln_ctx* ctx, double* A, int64_t m, int64_t ld
   if (bad) *bad = 0;
   if (m <= 0) return MLN_OK;
   constexpr int CB = 128;
-  double* Dinv = nullptr;
-  double* Ls = nullptr;
+  DevBuf<double> Dinv, Ls;
   const size_t mat = (size_t)m * (size_t)lda;
-  MLN_HIP(ctx, mln_dmalloc((void**)&Dinv, sizeof(double) * CB * CB * nbatch));
-  MLN_HIP(ctx, hipMemsetAsync(Dinv, 0, sizeof(double) * CB * CB * nbatch, ctx->stream));
+  MLN_TRY(Dinv.alloc_zeroed(ctx, CB * CB * nbatch, "Dinv"));
   MLN_HIP(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int) * 2, ctx->stream));
-  if (m > CB) MLN_HIP(ctx, mln_dmalloc((void**)&Ls, sizeof(double) * mat * nbatch));
+  if (m > CB) MLN_TRY(Ls.alloc(ctx, mat * nbatch, "Ls"));
   int rc = MLN_OK;
   auto batched = [&](GemmArgs& g, int64_t bsa, int64_t bsb, int64_t bsc) { if (nbatch > 1) { g.batch = nbatch; g.bsa = bsa; g.bsb = bsb; g.bsc = bsc; } };
   // Two block columns per round: the second one is brought up to date by a narrow GEMM (K = 128, 128 columns), and the
@@ -284,8 +282,6 @@ static int cholesky_lower_batched(mln_ctx* ctx, double* A, int64_t m, int64_t ld
   } else {
     (void)hipStreamSynchronize(ctx->stream);
   }
-  (void)mln_dfree(Dinv);
-  if (Ls) (void)mln_dfree(Ls);
   if (rc != MLN_OK) return rc;
   for (int b = nbatch - 1; b >= 0; --b)
     if (info[b] != 0) {
@@ -303,12 +299,6 @@ int dev_cholesky_lower2(mln_ctx* ctx, double* A, double* A2, int64_t m, int64_t 
 }
 
 // ---- triangular solves through block-scaled copies of the factor ------------------------------
-void triinv_free(TriInv* t) {
-  if (t->W) (void)mln_dfree(t->W);
-  if (t->W2) (void)mln_dfree(t->W2);
-  t->W = t->W2 = nullptr;
-}
-
 // W  (row-scaled):    W[j, <=j]  = Dinv_j [ -Lf[j,<j] | I ]     -> forward left-looking solves, X Lf^-T, backward updates
 // W2 (column-scaled): W2[>=j, j] = [ I ; -Lf[>j,j] ] Dinv_j     -> backward left-looking solves, forward updates
 // Both are built whatever the flags say: each is ONE launch of the GEMM kernel in its block-diagonal mode
@@ -321,9 +311,8 @@ int triinv_build(mln_ctx* ctx, const double* Lf, int64_t m, int64_t ld, bool nee
   out->ldf = ld;
   out->ld = ((m + 15) / 16) * 16;
   const size_t bytes = sizeof(double) * (size_t)m * (size_t)out->ld;
-  MLN_HIP(ctx, mln_dmalloc((void**)&out->W, bytes));
-  hipError_t e = mln_dmalloc((void**)&out->W2, bytes);
-  if (e != hipSuccess) { triinv_free(out); return mln_hip_fail(ctx, e, "alloc W2", __FILE__, __LINE__); }
+  MLN_TRY(out->W.alloc(ctx, (size_t)m * (size_t)out->ld, "W"));
+  if (const int rc2 = out->W2.alloc(ctx, (size_t)m * (size_t)out->ld, "W2")) { out->reset(); return rc2; }
   double* D = out->W;   // block-diagonal inverse first; the blocks under it follow
   MLN_HIP(ctx, hipMemsetAsync(D, 0, bytes, ctx->stream));
   const int64_t nb64 = (m + PB - 1) / PB, nb128 = (m + TB - 1) / TB;
@@ -344,7 +333,7 @@ int triinv_build(mln_ctx* ctx, const double* Lf, int64_t m, int64_t ld, bool nee
       rc = launch_dgemm(ctx, h);
     }
   }
-  if (rc != MLN_OK) { (void)hipStreamSynchronize(ctx->stream); triinv_free(out); mln_set_error(ctx, "triinv_build failed"); }
+  if (rc != MLN_OK) { (void)hipStreamSynchronize(ctx->stream); out->reset(); mln_set_error(ctx, "triinv_build failed"); }
   return rc;
 }
 

@@ -7,20 +7,7 @@
 #include <string>
 #include "../../include/mellon_hip.h"
 
-struct mln_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int n_cu = 0;
-  void* comm = nullptr;  // ncclComm_t when multi-GPU (one process per GPU)
-  struct mln_loopback* loop = nullptr;  // in-process thread-rank communicator (comm.hip)
-  int n_ranks = 1;
-  int rank = 0;
-  std::string err;
-  // grow-only device scratch
-  void* scratch = nullptr;
-  size_t scratch_bytes = 0;
-  int* d_info = nullptr;  // device int[4] for factorisation status
-};
+struct mln_ctx;
 
 void mln_set_error(mln_ctx* ctx, const std::string& msg);
 int mln_hip_fail(mln_ctx* ctx, hipError_t e, const char* what, const char* file, int line);
@@ -41,6 +28,29 @@ int mln_hip_fail(mln_ctx* ctx, hipError_t e, const char* what, const char* file,
 hipError_t mln_dmalloc(void** out, size_t bytes);
 hipError_t mln_dfree(void* p);
 void mln_dcache_flush();
+#include "dev_buf.h"
+
+struct mln_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int n_cu = 0;
+  void* comm = nullptr;  // ncclComm_t when multi-GPU (one process per GPU)
+  struct mln_loopback* loop = nullptr;  // in-process thread-rank communicator (comm.hip)
+  int n_ranks = 1;
+  int rank = 0;
+  std::string err;
+  // grow-only device scratch
+  DevBuf<char> scratch;
+  size_t scratch_bytes = 0;
+  DevBuf<int> d_info;  // device int[4] for factorisation status
+};
+
+template <class T, class Release>
+int DevBuf<T, Release>::alloc_zeroed(mln_ctx* ctx, size_t count, const char* what) {
+  MLN_TRY(alloc(ctx, count, what));
+  MLN_HIP(ctx, hipMemsetAsync(p_, 0, count * sizeof(T), ctx->stream));
+  return MLN_OK;
+}
 
 // ---- device-side covariance program (by-value kernel argument) ------------------------------
 struct DevLeaf {

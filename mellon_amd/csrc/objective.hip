@@ -773,10 +773,11 @@ static int launch_objective_wide(mln_ctx* ctx, const ObjArgs& a) {
     return MLN_ERR_UNSUPPORTED;
   }
   const bool gemvt = a.weights != nullptr, fonly = !gemvt && a.f_out != nullptr;
-  double *ftmp = nullptr, *coef = nullptr;
+  DevBuf<double> ftmp;
+  double* coef = nullptr;
   const int64_t n1 = a.n > 0 ? a.n : 1;
   if (!gemvt && !fonly) {
-    MLN_HIP(ctx, mln_dmalloc((void**)&ftmp, sizeof(double) * (size_t)n1 * 2));
+    MLN_TRY(ftmp.alloc(ctx, (size_t)n1 * 2, "ftmp"));
     coef = ftmp + n1;
   }
   int rc = MLN_OK;
@@ -808,7 +809,7 @@ static int launch_objective_wide(mln_ctx* ctx, const ObjArgs& a) {
       rc = launch_objective(ctx, s);
     }
   }
-  if (ftmp) { (void)hipStreamSynchronize(ctx->stream); (void)mln_dfree(ftmp); }
+  if (ftmp) (void)hipStreamSynchronize(ctx->stream);
   return rc;
 }
 

@@ -298,9 +298,9 @@ extern "C" int mln_objective_batch(mln_fit* f, const double* Z, int32_t S, doubl
                c_a1 = (size_t)std::max<int64_t>(n, 1) * sp_max, c_pl = (size_t)std::max<int64_t>(n_tiles, 1) * sp_max,
                c_part = (size_t)n_ranges * ldl * sp_max, c_out = (size_t)sp_max * (1 + m);
   auto even = [](size_t c) { return (c + 1) & ~(size_t)1; };
-  DevScratch sc(ctx);
-  MLN_HIP(ctx, sc.alloc(sizeof(double) * (even(c_z) + even(c_w) + even(c_lg) + even(c_a1) + even(c_pl) + even(c_part) + even(c_out))));
-  double* d_Z = sc.p;
+  DevBuf<double> sc;
+  MLN_TRY(sc.alloc(ctx, even(c_z) + even(c_w) + even(c_lg) + even(c_a1) + even(c_pl) + even(c_part) + even(c_out), "batched objective workspace"));
+  double* d_Z = sc;
   double* d_W = d_Z + even(c_z);
   double* d_lg = d_W + even(c_w);
   double* d_A1 = d_lg + even(c_lg);

@@ -163,45 +163,36 @@ __global__ __launch_bounds__(256) void k_gather_scale(const double* __restrict__
 
 int rebuild_select_rows(mln_ctx* ctx, const double* f_dev, const double* V_dev, int64_t n, int64_t row0,
                         double target_rows_global, uint64_t seed, RebuildSelection* out, double cap) {
-  out->rows = 0; out->idx = nullptr; out->scale = nullptr; out->w_max = 1.0; out->c = 0.0; out->sum_a = 0.0;
+  *out = RebuildSelection();
   const int nb = 256;
-  double *a = nullptr, *part = nullptr, *part2 = nullptr, *scal = nullptr;
+  DevBuf<double> a, part, part2, scal;
   const int64_t n1 = n > 0 ? n : 1;
-  MLN_HIP(ctx, mln_dmalloc((void**)&a, sizeof(double) * (size_t)n1));
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (a) (void)mln_dfree(a);
-    if (part) (void)mln_dfree(part);
-    if (part2) (void)mln_dfree(part2);
-    if (scal) (void)mln_dfree(scal);
-    return rc;
-  };
-  if (mln_dmalloc((void**)&part, sizeof(double) * nb) != hipSuccess || mln_dmalloc((void**)&part2, sizeof(double) * nb) != hipSuccess ||
-      mln_dmalloc((void**)&scal, sizeof(double) * 16) != hipSuccess) {
+  MLN_TRY(a.alloc(ctx, (size_t)n1, "a"));
+  if (part.alloc(ctx, nb, "part") != MLN_OK || part2.alloc(ctx, nb, "part2") != MLN_OK || scal.alloc(ctx, 16, "scal") != MLN_OK) {
     mln_set_error(ctx, "preconditioner rebuild: out of device memory");
-    return fail(MLN_ERR_HIP);
+    return MLN_ERR_HIP;
   }
-  hipLaunchKernelGGL(k_weights, dim3(nb), dim3(256), 0, ctx->stream, f_dev, V_dev, n, a, part, part2, cap);
-  hipLaunchKernelGGL(k_fold, dim3(1), dim3(64), 0, ctx->stream, part, nb, 0, scal);        // sum a  (this rank)
-  hipLaunchKernelGGL(k_fold, dim3(1), dim3(64), 0, ctx->stream, part2, nb, 1, scal + 1);   // max a  (this rank)
+  hipLaunchKernelGGL(k_weights, dim3(nb), dim3(256), 0, ctx->stream, f_dev, V_dev, n, a.get(), part.get(), part2.get(), cap);
+  hipLaunchKernelGGL(k_fold, dim3(1), dim3(64), 0, ctx->stream, part.get(), nb, 0, scal.get());        // sum a  (this rank)
+  hipLaunchKernelGGL(k_fold, dim3(1), dim3(64), 0, ctx->stream, part2.get(), nb, 1, scal + 1);   // max a  (this rank)
   int rc = comm_allreduce(ctx, scal, 1);
-  if (rc != MLN_OK) return fail(rc);
+  if (rc != MLN_OK) return rc;
   // the global maximum: every rank contributes its own (all-gather of one value per rank)
   const int nr = ctx->n_ranks > 1 ? ctx->n_ranks : 1;
-  double* gathered = nullptr;
-  if (mln_dmalloc((void**)&gathered, sizeof(double) * nr) != hipSuccess) return fail(MLN_ERR_HIP);
+  DevBuf<double> gathered;
+  MLN_TRY(gathered.alloc(ctx, nr, "gathered"));
   rc = (nr > 1) ? comm_allgather(ctx, scal + 1, gathered, 1)
                 : (hipMemcpyAsync(gathered, scal + 1, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess ? MLN_OK : MLN_ERR_HIP);
   std::vector<double> h(nr + 1);
   if (rc == MLN_OK && (hipMemcpyAsync(h.data(), gathered, sizeof(double) * nr, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                        hipMemcpyAsync(h.data() + nr, scal, sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                        hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = MLN_ERR_HIP;
-  (void)mln_dfree(gathered);
-  if (rc != MLN_OK) return fail(rc);
+  gathered.reset();
+  if (rc != MLN_OK) return rc;
   double a_max = 0.0;
   for (int r = 0; r < nr; ++r) a_max = std::max(a_max, h[r]);
   const double sum_a = h[nr];
-  if (!(sum_a > 0.0) || !std::isfinite(sum_a)) { mln_set_error(ctx, "preconditioner rebuild: degenerate weights"); return fail(MLN_ERR_ARG); }
+  if (!(sum_a > 0.0) || !std::isfinite(sum_a)) { mln_set_error(ctx, "preconditioner rebuild: degenerate weights"); return MLN_ERR_ARG; }
   // c with  g(c) = sum_i min(1, c a_i) = target.  g is concave, increasing and piecewise linear; Newton's iteration from the
   // left (c0 = target / sum a <= c*, since min(1, x) <= x) rises monotonically and never overshoots -- a tangent of a concave
   // function lies above it -- and lands exactly once no breakpoint is left between the iterate and c*: 3-4 rounds where the
@@ -209,13 +200,13 @@ int rebuild_select_rows(mln_ctx* ctx, const double* f_dev, const double* V_dev, 
   // 0.5 ms of a C2 step, 0.7-1 ms on 8 ranks).  Every rank computes the same c from the same all-reduced pair.
   double c = target_rows_global / sum_a;
   for (int it = 0; it < 14; ++it) {
-    hipLaunchKernelGGL(k_expected, dim3(nb), dim3(256), 0, ctx->stream, a, n, c, part, part2);
-    hipLaunchKernelGGL(k_fold2, dim3(1), dim3(64), 0, ctx->stream, part, part2, nb, scal + 2);
+    hipLaunchKernelGGL(k_expected, dim3(nb), dim3(256), 0, ctx->stream, a.get(), n, c, part.get(), part2.get());
+    hipLaunchKernelGGL(k_fold2, dim3(1), dim3(64), 0, ctx->stream, part.get(), part2.get(), nb, scal + 2);
     rc = comm_allreduce(ctx, scal + 2, 2);
     double gs[2] = {0.0, 0.0};
     if (rc == MLN_OK && (hipMemcpyAsync(gs, scal + 2, sizeof(gs), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                          hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = MLN_ERR_HIP;
-    if (rc != MLN_OK) return fail(rc);
+    if (rc != MLN_OK) return rc;
     const double cnt = gs[0], slope = gs[1];
     if (!(cnt > 0.0)) break;
     if (std::fabs(target_rows_global / cnt - 1.0) < 1e-3) break;
@@ -229,15 +220,12 @@ int rebuild_select_rows(mln_ctx* ctx, const double* f_dev, const double* V_dev, 
   // in [0, 1] (the range the integer Gram quantises) and the Gram is multiplied back by w_max
   const double w_max = std::max(a_max, 1.0 / c);
   const int64_t n_blk = (n + SB - 1) / SB;
-  int* counts = nullptr;
-  int64_t* offsets = nullptr;
+  DevBuf<int> counts;
+  DevBuf<int64_t> offsets;
   if (n_blk > 0) {
-    if (mln_dmalloc((void**)&counts, sizeof(int) * (size_t)n_blk) != hipSuccess ||
-        mln_dmalloc((void**)&offsets, sizeof(int64_t) * (size_t)n_blk) != hipSuccess) {
-      if (counts) (void)mln_dfree(counts);
-      return fail(MLN_ERR_HIP);
-    }
-    hipLaunchKernelGGL(k_select_count, dim3((unsigned)n_blk), dim3(256), 0, ctx->stream, a, n, c, row0, seed, counts);
+    MLN_TRY(counts.alloc(ctx, (size_t)n_blk, "counts"));
+    MLN_TRY(offsets.alloc(ctx, (size_t)n_blk, "offsets"));
+    hipLaunchKernelGGL(k_select_count, dim3((unsigned)n_blk), dim3(256), 0, ctx->stream, a.get(), n, c, row0, seed, counts.get());
     std::vector<int> hc((size_t)n_blk);
     std::vector<int64_t> ho((size_t)n_blk);
     if (hipMemcpyAsync(hc.data(), counts, sizeof(int) * (size_t)n_blk, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
@@ -245,31 +233,24 @@ int rebuild_select_rows(mln_ctx* ctx, const double* f_dev, const double* V_dev, 
     int64_t total = 0;
     for (int64_t b = 0; b < n_blk && rc == MLN_OK; ++b) { ho[(size_t)b] = total; total += hc[(size_t)b]; }
     if (rc == MLN_OK && total > 0) {
-      if (mln_dmalloc((void**)&out->idx, sizeof(int64_t) * (size_t)total) != hipSuccess ||
-          mln_dmalloc((void**)&out->scale, sizeof(double) * (size_t)total) != hipSuccess) rc = MLN_ERR_HIP;
+      rc = out->idx.alloc(ctx, (size_t)total, "idx");
+      if (rc == MLN_OK) rc = out->scale.alloc(ctx, (size_t)total, "scale");
       if (rc == MLN_OK && hipMemcpyAsync(offsets, ho.data(), sizeof(int64_t) * (size_t)n_blk, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         rc = MLN_ERR_HIP;
       if (rc == MLN_OK) {
-        hipLaunchKernelGGL(k_select_write, dim3((unsigned)n_blk), dim3(64), 0, ctx->stream, a, n, c, row0, seed, offsets,
-                           1.0 / w_max, out->idx, out->scale);
+        hipLaunchKernelGGL(k_select_write, dim3((unsigned)n_blk), dim3(64), 0, ctx->stream, a.get(), n, c, row0, seed, offsets.get(),
+                           1.0 / w_max, out->idx.get(), out->scale.get());
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = MLN_ERR_HIP;
       }
     }
-    (void)mln_dfree(counts);
-    (void)mln_dfree(offsets);
-    if (rc != MLN_OK) { rebuild_selection_free(ctx, out); mln_set_error(ctx, "preconditioner rebuild: row selection failed"); return fail(rc); }
+    counts.reset();
+    offsets.reset();
+    if (rc != MLN_OK) { (void)hipStreamSynchronize(ctx->stream); out->reset(); mln_set_error(ctx, "preconditioner rebuild: row selection failed"); return rc; }
     out->rows = total;
   }
   out->w_max = w_max; out->c = c; out->sum_a = sum_a;
-  (void)fail(MLN_OK);
-  return MLN_OK;
-}
-
-void rebuild_selection_free(mln_ctx* ctx, RebuildSelection* s) {
   (void)hipStreamSynchronize(ctx->stream);
-  if (s->idx) (void)mln_dfree(s->idx);
-  if (s->scale) (void)mln_dfree(s->scale);
-  s->idx = nullptr; s->scale = nullptr; s->rows = 0;
+  return MLN_OK;
 }
 
 int launch_gather_scale_rows(mln_ctx* ctx, const double* A, int64_t ld, const int64_t* idx, const double* scale,

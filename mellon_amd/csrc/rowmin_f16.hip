@@ -24,7 +24,6 @@
 
 #include "mln_internal.h"
 
-hipError_t mln_dfree_synced(void* p);   // alloc.hip: release after the caller synchronised the only stream that used p
 #include "rowmin_f16.h"
 // rowmin_w64.hip: the folded sweep, one wave per SIMD (round 6)
 int launch_rowmin_w64(mln_ctx* ctx, const _Float16* X, int64_t n, const _Float16* Y, int64_t m, int64_t self_offset, int exclude_self,
@@ -921,15 +920,16 @@ static int nn_search_core(mln_ctx* ctx, const double* x, int64_t n, const double
   double *xx = nullptr, *yy = nullptr, *ymax = nullptr, *prep = nullptr;
   float *yyf = nullptr, *m1 = nullptr, *m2 = nullptr;
   int *arg = nullptr, *nflag = nullptr, *flagged = nullptr;
-  std::vector<void*> owned;
+  std::vector<StreamBuf<char>> owned;   // used on ctx->stream only, which cleanup drains
   auto alloc = [&](void** p, size_t bytes) -> bool {
-    if (mln_dmalloc(p, bytes > 0 ? bytes : 8) != hipSuccess) return false;
-    owned.push_back(*p);
+    owned.emplace_back();
+    if (owned.back().alloc(ctx, bytes > 0 ? bytes : 8, "1-NN search workspace") != MLN_OK) return false;
+    *p = owned.back().get();
     return true;
   };
   auto cleanup = [&](int rc) {
     (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : owned) (void)mln_dfree_synced(p);
+    owned.clear();
     return rc;
   };
   const int fold = (d <= KP - 3) ? 1 : 0;       // (three spare k slots carry |y|^2)
@@ -1150,15 +1150,16 @@ int kmeans_lloyd_from(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int64
 static int nn_distances_pruned(mln_ctx* ctx, const double* x, int64_t n, int d, double* out, double* stats) {
   int Kc = (int)std::min<int64_t>(1024, std::max<int64_t>(64, n / 2048));
   const int64_t ns = std::min<int64_t>(n, (int64_t)64 * Kc), stride = n / ns;
-  std::vector<void*> owned;
+  std::vector<StreamBuf<char>> owned;   // used on ctx->stream only, which cleanup drains
   auto alloc = [&](void** p, size_t bytes) -> bool {
-    if (mln_dmalloc(p, bytes > 0 ? bytes : 8) != hipSuccess) return false;
-    owned.push_back(*p);
+    owned.emplace_back();
+    if (owned.back().alloc(ctx, bytes > 0 ? bytes : 8, "1-NN search workspace") != MLN_OK) return false;
+    *p = owned.back().get();
     return true;
   };
   auto cleanup = [&](int rc) {
     (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : owned) (void)mln_dfree_synced(p);
+    owned.clear();
     return rc;
   };
   double *sample = nullptr, *cent = nullptr, *prep = nullptr, *radius = nullptr, *xsorted = nullptr, *osorted = nullptr;

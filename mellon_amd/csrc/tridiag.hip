@@ -120,8 +120,8 @@ int64_t sturm_count(const std::vector<double>& d, const std::vector<double>& e, 
 // A (m x m symmetric, full storage, DESTROYED) -> number of eigenvalues above tol2 * lambda_max; lambda_max returned too
 int dev_sym_rank_above(mln_ctx* ctx, double* A, int64_t m, int64_t ld, double tol2, int64_t* rank, double* lambda_max) {
   if (m <= 0) { *rank = 0; if (lambda_max) *lambda_max = 0.0; return MLN_OK; }
-  double* work = nullptr;   // v, p, w (m each), d, e (m each), tau
-  MLN_HIP(ctx, mln_dmalloc((void**)&work, sizeof(double) * (size_t)(5 * m + 8)));
+  DevBuf<double> work;   // v, p, w (m each), d, e (m each), tau
+  MLN_TRY(work.alloc(ctx, (size_t)(5 * m + 8), "work"));
   double *v = work, *p = work + m, *w = work + 2 * m, *dd = work + 3 * m, *de = work + 4 * m, *tau = work + 5 * m;
   for (int64_t k = 0; k + 2 < m; ++k) {
     const int64_t s = m - k - 1;
@@ -143,7 +143,7 @@ int dev_sym_rank_above(mln_ctx* ctx, double* A, int64_t m, int64_t ld, double to
     err = hipMemcpyAsync(&tail[2], A, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   }
   if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-  (void)mln_dfree(work);
+  work.reset();
   if (err != hipSuccess) return mln_hip_fail(ctx, err, "tridiagonalisation", __FILE__, __LINE__);
   if (m >= 2) { d[m - 2] = tail[0]; e[m - 2] = tail[1]; }
   d[m - 1] = tail[2];
