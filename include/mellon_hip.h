@@ -374,6 +374,18 @@ int mln_fit_set_dim_likelihood(mln_fit* fit, const double* ell, int32_t k, doubl
 int mln_dim_objective(mln_fit* fit, const double* z, double* loss, double* grad /* 2 x m */,
                       double* hess_diag /* 2 x m or NULL */);
 
+/* mln_dim_objective at S points in one call (the Monte-Carlo step of DimensionalityEstimator(optimizer="advi")):
+ * loss[s], grad[s][:][:] = mln_dim_objective(fit, Z[s][:][:]) without the Hessian.  Z, grad: S x 2 x m row-major (sample s,
+ * then row 0 the log-dimensionality, row 1 the log-density); loss: S.  Any S >= 1 (chunks of 32 samples inside: each
+ * sample takes two columns of the skinny products, one per latent function).  Same likelihood
+ * (mln_fit_set_dim_likelihood, hence the same 5120-landmark limit), same all-reduce over ranks (one per chunk: the
+ * losses and the gradient block together), prior terms added once per sample; a non-finite loss is returned as +inf.
+ * Two passes over the n x m buffer per chunk instead of one per sample: F = B [W0 | W1] with the Poisson likelihood in
+ * the epilogue, then G = B^T [C0 | C1], on the fp64 matrix cores (csrc/dim_objective_batch.hip).  Every handle layout is
+ * batched: explicit and implicit factors, Nystroem projections, mln_fit_from_L, the full GP.  Bit-reproducible from
+ * call to call. */
+int mln_dim_objective_batch(mln_fit* fit, const double* Z, int32_t S, double* loss /* S */, double* grad /* S x 2 x m */);
+
 /* a-11: f = L z + mu on this shard (inference.py:51-69,341-354).                                */
 int mln_transform(mln_fit* fit, const double* z, double mu, double* f_out /* n_local */);
 

@@ -2,6 +2,8 @@
 prepare_inference / run_inference / process_inference / fit / fit_predict flow, `predict` (local dimensionality) and
 `predict_density`.  The k-NN search, the local fractal dimension, the covariance factorisation and the MAP objective of
 the (log-dimensionality, log-density) pair run on the MI355X; SciPy's L-BFGS-B drives the objective from the host.
+optimizer="advi" fits a mean-field Gaussian over both latent functions (inference.run_advi on the batched objective,
+mln_dim_objective_batch); `pre_transformation_std` is then (2, m), one row per predictor.
 
 Deliberate deviation: duplicate cells give a zero nearest-neighbour distance and log 0 in the likelihood; the reference's
 solve then sees an infinite loss and stops where it started.  This estimator raises a ValueError naming the count of
@@ -211,6 +213,10 @@ class DimensionalityEstimator(BaseEstimator):
         return self.loss_func, self.initial_value
 
     def run_inference(self, loss_func=None, initial_value=None, optimizer=None):
+        if optimizer == "advi" and self.optimizer != "advi":
+            # the one remaining limit: a prepared estimator is not switched to ADVI here (everything below serves it)
+            raise NotImplementedError('run_inference does not switch a prepared DimensionalityEstimator to "advi": '
+                                      'construct the estimator with optimizer="advi".')
         if loss_func is not None:
             self.loss_func = loss_func
         if initial_value is not None:

@@ -175,6 +175,13 @@ class DimensionalityLossFunc:
         loss, grad = self.fit.dim_objective(self._split(z))
         return loss, grad.reshape(np.shape(z))
 
+    def value_and_grad_batch(self, Z):
+        """(loss[S], grad) at the S points of Z, (S, 2, m) or the flat (S, 2 m) that run_advi passes, grad in the shape
+        of Z: one batched device call (mln_dim_objective_batch)."""
+        Z = np.asarray(Z, dtype=np.float64)
+        self.n_eval += Z.shape[0]
+        return self.fit.dim_objective_batch(Z)
+
     def value_and_grad_u(self, u):
         self.n_eval += 1
         uu = self._split(u)
@@ -292,13 +299,14 @@ def run_advi(loss_func, initial_parameters, n_iter=DEFAULT_N_ITER, init_learn_ra
       value      = mean_s[loss(z_s) + log q(z_s)],  log q(z_s) = sum_j(-eps_sj^2 / 2 - log_std_j - log(2 pi) / 2)
       d / d mean = mean_s grad loss(z_s);  d / d log_std = exp(log_std) * mean_s(grad loss(z_s) * eps_s) - 1
     (what jax.value_and_grad of inference.py:848-850 yields).  The `nsamples` losses and gradients of a step are ONE
-    batched device call (loss_func.value_and_grad_batch -> mln_objective_batch): two passes over the n x m buffer instead
-    of `nsamples`.  losses[t] is the value at the parameters before update t: -ELBO, as in the reference (whose
+    batched device call (loss_func.value_and_grad_batch -> mln_objective_batch, or mln_dim_objective_batch for the
+    dimensionality loss, whose (2, m) parameters are drawn and passed flat): two passes over the n x m buffer per chunk of
+    samples instead of `nsamples`.  losses[t] is the value at the parameters before update t: -ELBO, as in the reference (whose
     variable is misnamed `elbo`).  Returns (pre_transformation, pre_transformation_std = exp(log_std), losses)."""
     batch = getattr(loss_func, "value_and_grad_batch", None)
     if batch is None:
-        raise NotImplementedError("optimizer 'advi' needs a loss with value_and_grad_batch (compute_loss_func returns one); "
-                                  "it is not available for plain callables or the dimensionality loss.")
+        raise NotImplementedError("optimizer 'advi' needs a loss with value_and_grad_batch (compute_loss_func and "
+                                  "compute_dimensionality_loss_func return one); it is not available for plain callables.")
     mean = np.array(initial_parameters, dtype=np.float64)
     log_std = np.zeros_like(mean)
     m = mean.size

@@ -4,6 +4,11 @@ the same shape; the likelihood between them is left out, so this is a lower boun
 run_advi on the handle.  Prints one JSON line per measurement.
 
     python tools/advi_probe.py --shape c3|c2 [--batch-only] [--steps 100]
+    python tools/advi_probe.py --dim [--explicit] [--batch-only]
+
+--dim measures the dimensionality objective instead (DimensionalityEstimator(optimizer="advi")): one mln_dim_objective
+call, S of them, and one mln_dim_objective_batch call on the same handle at 2e5 cells x 5000 landmarks, k = 10 (synthetic
+sorted distances); implicit handle unless --explicit.
 
 Shapes: c3 = 1e6 cells x 50 dims, 5000 landmarks; c2 = 1e5 x 20, 1000; implicit handle (the estimators' default).
 Landmarks are random cells and the nearest-neighbour distances synthetic: the timings do not depend on either.
@@ -47,13 +52,62 @@ class _BatchLoss:
         return self.fit.objective_batch(Z)
 
 
+DIM_SHAPE = (200_000, 20, 5000, 10)      # cells, dims, landmarks, neighbours
+DIM_CHUNK = 32                           # samples per chunk of mln_dim_objective_batch
+
+
+def dim_main(args):
+    import bench
+    from mellon_amd import _lib, cov
+    n, d, m, k = DIM_SHAPE
+    S = args.samples
+    ctx = _lib.default_context()
+    x = bench.gaussian_mixture(n, d, 3)
+    rng = np.random.default_rng(0)
+    xu = np.ascontiguousarray(x[rng.choice(n, size=m, replace=False)])
+    ell = np.log(np.sort(np.abs(rng.standard_normal((n, k))) + 0.05, axis=-1)) + np.log(np.pi) / 2
+    fit = ctx.fit_prepare(cov.Matern52(float(np.sqrt(d))).lower(d), x, xu, 1e-6, implicit=not args.explicit)
+    fit.set_dim_likelihood(ell, 0.3, 1.1)
+    Z = 0.05 * rng.standard_normal((S, 2, m))
+    fit.dim_objective_batch(Z[:2])                # module load, Lp factorisation
+    fit.dim_objective_batch(Z)
+    fit.dim_objective(Z[0])
+    if args.batch_only:
+        for _ in range(3):
+            fit.dim_objective_batch(Z)
+        return
+    chunks = (S + DIM_CHUNK - 1) // DIM_CHUNK
+    common = dict(shape="dim", handle="explicit" if args.explicit else "implicit", n=n, m=m, k=k, S=S)
+    # the two versions alternate, so that a change of the machine's load between them shows in the spread
+    t_single, t_batch = [], []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        singles = [fit.dim_objective(z) for z in Z]
+        t1 = time.perf_counter()
+        loss, grad = fit.dim_objective_batch(Z)
+        t2 = time.perf_counter()
+        t_single.append(t1 - t0)
+        t_batch.append(t2 - t1)
+    e_loss = max(abs(loss[s] - singles[s][0]) / abs(singles[s][0]) for s in range(S))
+    e_grad = max(np.abs(grad[s] - singles[s][1]).max() / np.abs(singles[s][1]).max() for s in range(S))
+    ts, tb = float(np.median(t_single)), float(np.median(t_batch))
+    emit(what="dim_objective_x_S", seconds=ts, min=min(t_single), max=max(t_single), **common)
+    emit(what="dim_objective_batch", seconds=tb, min=min(t_batch), max=max(t_batch), ratio_to_S_single_passes=tb / ts,
+         speedup=ts / tb, speedup_from_traffic_alone=S / (2.0 * chunks), buffer_reads=2 * chunks,
+         buffer_gb_per_s=2 * chunks * 8.0 * n * m / tb / 1e9, max_rel_loss_diff=e_loss, max_rel_grad_diff=e_grad, **common)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dim", action="store_true")
+    ap.add_argument("--explicit", action="store_true")
     ap.add_argument("--shape", choices=sorted(SHAPES), default="c3")
     ap.add_argument("--samples", type=int, default=40)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--batch-only", action="store_true")
     args = ap.parse_args()
+    if args.dim:
+        return dim_main(args)
     import bench
     from mellon_amd import _lib, cov, inference
     n, d, m = SHAPES[args.shape]
