@@ -467,6 +467,12 @@ int mln_diag_gram_i8(mln_ctx* ctx, const double* A, int64_t rows, int64_t m, dou
 /* ms of: kernel-matrix pass alone, Gram GEMM alone, both on two streams, Cholesky alone, kernel matrix ||
  * Cholesky, kernel matrix || (Cholesky then Gram) -- the measurement behind the two-stream set-up phase. */
 int mln_diag_overlap(mln_ctx* ctx, int64_t n, int64_t m, int32_t d, int64_t gram_rows, double* out /* 6 */);
+/* One launch of the fp64 objective kernel over `count` rows of the fit's buffer: first + i * stride (rows == NULL), or
+ * rows[i] with optional per-row weights on the likelihood term.  Host pointers.  loss: the likelihood sum (times out_scale
+ * when that is non-zero), grad (m): the rows' part of the gradient, f_rows (count): f of the rows in launch order; no prior. */
+int mln_diag_objective_rows(mln_fit* fit, const double* z, int64_t count, int64_t first, int64_t stride,
+                            const int64_t* rows, const double* row_w, double out_scale, double* loss, double* grad,
+                            double* f_rows);
 
 /* ---- predictive uncertainty (S8f rank 2) ----------------------------------------------------------
  * covariance:       k(x*,x*) - A A^T with A = cov(x*, centers) Lf^-T      conditional.py:409-422,930-945
@@ -493,8 +499,11 @@ int mln_predict_mean_covariance(mln_ctx* ctx, const mln_kernel_desc* cov, const 
  * than 1e5) or lost positive definiteness -- the solve went on with the first preconditioner; [19] rebuilt preconditioners
  * that failed their trial (no convergence within 60 iterations) and were replaced by the first again; [20] halvings of a
  * start whose loss was not finite or above 1e30; [21] how the last mln_fit_gram_rank counted: 1 = inertia of G - x I
- * (csrc/ldl_inertia.hip), 2 = tridiagonalisation + Sturm counts (csrc/tridiag.hip), 0 = not called.                       */
-#define MLN_N_STAGE_TIMES 22
+ * (csrc/ldl_inertia.hip), 2 = tridiagonalisation + Sturm counts (csrc/tridiag.hip), 0 = not called; importance tail of
+ * mln_map_solve (passes over an importance-sampled row list after the rebuild): [22] launches -- not in [6], counted in [17]
+ * by rows / n --, [23] rows of this rank's list, [24] kernel seconds, [25] times its guard fired (the full loss rose: the
+ * solve went back to the last anchor and finished on full passes).                                                        */
+#define MLN_N_STAGE_TIMES 26
 int mln_stage_times(mln_fit* fit, double* out /* MLN_N_STAGE_TIMES */);
 
 #ifdef __cplusplus

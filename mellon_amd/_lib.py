@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libmellon_hip.so")
 
 MLN_OK, MLN_ERR_NOT_PD, MLN_ERR_SHAPE, MLN_ERR_HIP, MLN_ERR_RCCL, MLN_ERR_ARG, MLN_ERR_UNSUPPORTED = range(7)
 MLN_UNIQUE_ID_BYTES = 128
-MLN_N_STAGE_TIMES = 22
+MLN_N_STAGE_TIMES = 26
 
 K_MATERN32, K_MATERN52, K_EXPQUAD, K_EXPONENTIAL, K_RATQUAD, K_LINEAR, K_DISTANCE = 1, 2, 3, 4, 5, 6, 7
 OP_LEAF, OP_CONST, OP_ADD, OP_MUL, OP_POW = 0, 1, 2, 3, 4
@@ -129,6 +129,7 @@ SYMBOLS = [
     ("mln_stage_times", C.c_int, [_vp, _dp]),
     ("mln_diag_peak", C.c_int, [_vp, _i32, _i64, C.POINTER(_dbl)]),
     ("mln_diag_overlap", C.c_int, [_vp, _i64, _i64, _i32, _i64, _dp]),
+    ("mln_diag_objective_rows", C.c_int, [_vp, _dp, _i64, _i64, _i64, _vp, _dp, _dbl, C.POINTER(_dbl), _dp, _dp]),
     ("mln_diag_gram_i8", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, C.POINTER(_dbl)]),
     ("mln_diag_dgemm", C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _i32, C.POINTER(_dbl)]),
     ("mln_diag_dgemm_compare", C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _dbl, _i32, C.POINTER(_dbl)]),
@@ -1152,6 +1153,25 @@ class Fit:
                         jitter="ridge")
         return z, loss.value, nev.value, nit.value, st.value
 
+    def objective_rows(self, z, count=None, first=0, stride=1, rows=None, weights=None, out_scale=0.0):
+        """One launch of the objective kernel over a row subset (mln_diag_objective_rows): the strided launch, or the row
+        list with optional weights.  Returns (likelihood sum, the rows' part of the gradient, f of the rows)."""
+        z = _f64(z)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            count = rows.shape[0]
+        if weights is not None:
+            weights = _f64(weights)
+            assert rows is not None and weights.shape[0] == count
+        loss = C.c_double()
+        grad = np.empty(self.m, dtype=np.float64)
+        f = np.empty(int(count), dtype=np.float64)
+        self._check(self.lib.mln_diag_objective_rows(self.handle, z.ctypes.data, int(count), int(first), int(stride),
+                                                     None if rows is None else rows.ctypes.data,
+                                                     None if weights is None else weights.ctypes.data, float(out_scale),
+                                                     C.byref(loss), grad.ctypes.data, f.ctypes.data))
+        return loss.value, grad, f
+
     def transform(self, z, mu, out=None):
         z = _f64(z)
         ret = np.empty(self.n, dtype=np.float64) if out is None else out
@@ -1179,7 +1199,8 @@ class Fit:
                 "objective32_kernel_s", "objective32_launches", "copy32_format", "emulation_excluded_s",
                 "objective_sub_kernel_s", "objective_sub_launches", "objective_sub_stride", "precond_rebuild_s",
                 "precond_rebuilds", "objective_pass_equivalents", "precond_rebuilds_declined", "precond_reverts",
-                "start_halvings", "rank_path"]
+                "start_halvings", "rank_path", "objective_tail_launches", "objective_tail_rows",
+                "objective_tail_kernel_s", "objective_tail_guard"]
         return dict(zip(keys, out.tolist()))
 
 

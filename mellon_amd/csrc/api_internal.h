@@ -164,6 +164,11 @@ struct mln_fit {
   double build_seconds = 0.0;     // wall time of the first preconditioner build (Gram + factorisation): the rebuild's price
   double times_sub = 0.0, times_rebuild = 0.0, sub_pass_equiv = 0.0;
   int evals_sub = 0, n_rebuild = 0;
+  // importance tail of the MAP solve (solver.h): the row list drawn at the pause (alive while the solve runs), accounting
+  RebuildSelection tail_sel;
+  double times_tail = 0.0;
+  int evals_tail = 0, n_tail_guard = 0;
+  int64_t tail_rows = 0;
   // dimensionality likelihood (dimensionality.hip): ell = log(sorted k-NN distance) + log(pi) / 2 (n x dim_k), the two means,
   // the partials of one pass (n_wg x 4 ldl: both gradients, both Hessian diagonals), z and w (4 ldl), the reduced sums
   DevBuf<double> dim_ell;
@@ -187,7 +192,8 @@ void obj_account(mln_fit* f, bool f32 = false);
 int fit_w_from_z(mln_fit* f, const double* z_dev, double* w_dev, const double* z_host = nullptr);
 int fit_cache_pair_from_u(mln_fit* f, const double* u_dev);
 int fit_enqueue_eval(mln_fit* f, const double* u_dev, double* gn_dev, bool use32, const int* gate,
-                            hipEvent_t* ev, const std::vector<int64_t>* sub_strides = nullptr);
+                            hipEvent_t* ev, const std::vector<int64_t>* sub_strides = nullptr,
+                            const RebuildSelection* tail = nullptr);
 int fit_objective_u(mln_fit* f, const double* u, double* loss, double* grad_u, double* z_out,
                            bool use32 = false);
 int fit_solver_alloc(mln_fit* f, int maxcor);

@@ -88,6 +88,59 @@ extern "C" int mln_objective(mln_fit* f, const double* z, double* loss, double* 
   return MLN_OK;
 }
 
+// One launch of the fp64 objective kernel over a row SUBSET of the buffer, for tests and measurements of the kernel itself:
+// `count` rows, either first + i * stride (rows == NULL: the launch the solver's subsample phase makes) or rows[i] with
+// optional weights (the launch its importance tail makes).  Host pointers.  Returns what the launch and the fixed-order
+// reduction leave -- the likelihood sum (times out_scale), L^T (coefficients) (m), and f of the rows in launch order -- with
+// no prior term.  `z` is the vector the kernel streams against (implicit fits: w = Lp^-T z).
+extern "C" int mln_diag_objective_rows(mln_fit* f, const double* z, int64_t count, int64_t first, int64_t stride,
+                                       const int64_t* rows, const double* row_w, double out_scale, double* loss,
+                                       double* grad, double* f_rows) {
+  if (!f || !z || !loss || !grad || !f_rows || count < 1) return MLN_ERR_ARG;
+  mln_ctx* ctx = f->ctx;
+  if (!f->V) { mln_set_error(ctx, "mln_fit_set_likelihood has not been called"); return MLN_ERR_ARG; }
+  if (f->m > objective_max_m_one_pass() || !objective_can_keep_f(count, f->n_wg)) {
+    mln_set_error(ctx, "mln_diag_objective_rows: shape beyond the one-pass kernel / its f staging");
+    return MLN_ERR_UNSUPPORTED;
+  }
+  bool ok = true;
+  if (rows) { for (int64_t i = 0; i < count; ++i) ok = ok && rows[i] >= 0 && rows[i] < f->n; }
+  else ok = stride >= 1 && first >= 0 && first + (count - 1) * stride < f->n;
+  if (!ok) { mln_set_error(ctx, "mln_diag_objective_rows: rows outside the buffer"); return MLN_ERR_ARG; }
+  MLN_HIP(ctx, hipSetDevice(ctx->device));
+  DevBuf<double> fk, wd;
+  DevBuf<int64_t> rd;
+  DevBuf<int> slot;
+  MLN_TRY(fk.alloc_zeroed(ctx, 2 * (size_t)count, "diag f"));
+  MLN_TRY(slot.alloc_zeroed(ctx, 1, "diag slot"));
+  MLN_HIP(ctx, hipMemcpyAsync(f->d_z, z, sizeof(double) * f->m, hipMemcpyHostToDevice, ctx->stream));
+  ObjArgs a = obj_args(f);
+  a.n = count; a.out_scale = out_scale;
+  a.f_keep[0] = fk; a.f_keep[1] = fk + count; a.f_slot = slot;     // slot 0: the pass writes f_keep[1]
+  if (rows) {
+    MLN_TRY(rd.alloc(ctx, (size_t)count, "diag rows"));
+    MLN_HIP(ctx, hipMemcpyAsync(rd, rows, sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    a.rows = rd;
+    if (row_w) {
+      MLN_TRY(wd.alloc(ctx, (size_t)count, "diag weights"));
+      MLN_HIP(ctx, hipMemcpyAsync(wd, row_w, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+      a.row_w = wd;
+    }
+  } else {
+    a.row_first = first; a.row_stride = stride;
+  }
+  int rc = launch_objective(ctx, a);
+  if (rc == MLN_OK) rc = launch_reduce_obj(ctx, a, f->d_out);
+  if (rc == MLN_OK && (hipMemcpyAsync(f->h_out, f->d_out, sizeof(double) * (1 + f->m), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                       hipMemcpyAsync(f_rows, fk + count, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+    rc = MLN_ERR_HIP;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MLN_OK) rc = MLN_ERR_HIP;
+  if (rc != MLN_OK) return rc;
+  *loss = f->h_out[0];
+  std::memcpy(grad, f->h_out + 1, sizeof(double) * f->m);
+  return MLN_OK;
+}
+
 extern "C" int mln_transform(mln_fit* f, const double* z, double mu, double* f_out) {
   if (!f || !z || (f->n > 0 && !f_out)) return MLN_ERR_ARG;
   mln_ctx* ctx = f->ctx;
@@ -122,8 +175,10 @@ extern "C" int mln_transform(mln_fit* f, const double* z, double mu, double* f_o
 // gate == nullptr: `use32` picks the streamed copy.  gate != nullptr (device-resident solver): both objective kernels
 // are launched and the one the solver's state does not select returns at once; everything is a no-op after DONE.
 // ev (optional): three events -- before the fp32 pass, between the two, after the fp64 pass.
+// tail (optional, gated solves only): the importance-sampled row list of the solve's last phase -- one more launch of the
+// fp64 kernel, over those rows with their weights, that works while the solver's gate is MLN_GATE_TAIL.
 int fit_enqueue_eval(mln_fit* f, const double* u_dev, double* gn_dev, bool use32, const int* gate,
-                            hipEvent_t* ev, const std::vector<int64_t>* sub_strides) {
+                            hipEvent_t* ev, const std::vector<int64_t>* sub_strides, const RebuildSelection* tail) {
   mln_ctx* ctx = f->ctx;
   const int64_t m = f->m, ld = f->ldl, ld2 = f->ld2;
   if (f->kspace) {
@@ -170,6 +225,21 @@ int fit_enqueue_eval(mln_fit* f, const double* u_dev, double* gn_dev, bool use32
       as.gate2 = &f->sv.st->sub_level; as.gate2_want = (int)lv;
       MLN_TRY(launch_objective(ctx, as));
     }
+  }
+  if (gate && tail) {
+    // same grid and partial buffers as the full pass (workgroups past the list's end write zero partials); no out_scale:
+    // the weights 1 / p_i make the sums stand for all cells.  It keeps no f: the rows' f of the last FULL pass stay put.
+    // (A rank whose draw kept no row has no list.  Its launch is still made, over zero rows of the plain row map: every
+    //  workgroup then writes zero partials, which the reduction needs -- the full-size launch is gated off in this phase.)
+    ObjArgs at = a;
+    at.n = tail->rows > 0 ? tail->rows : 0;
+    at.rows = tail->rows > 0 ? tail->idx.get() : nullptr;
+    at.row_w = tail->rows > 0 ? tail->scale.get() : nullptr;
+    at.row_stride = 0; at.row_first = 0; at.out_scale = 0.0;
+    at.f_keep[0] = at.f_keep[1] = nullptr; at.f_slot = nullptr;
+    at.gate_want = MLN_GATE_SUB;
+    at.gate2 = &f->sv.st->sub_level; at.gate2_want = MLN_TAIL_LEVEL;
+    MLN_TRY(launch_objective(ctx, at));
   }
   if (ev) MLN_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
   MLN_TRY(launch_reduce_obj2(ctx, a, f->d_zr + ld2 + m, f->d_zr + ld2));
@@ -236,7 +306,7 @@ int fit_solver_alloc(mln_fit* f, int maxcor) {
   if (f->sv_block && f->sv_maxcor >= maxcor) return MLN_OK;
   if (f->sv_block) { MLN_HIP(ctx, hipStreamSynchronize(ctx->stream)); f->sv_block.reset(); }
   const size_t ld = (size_t)f->ldl;
-  const size_t n_dbl = 6 * ld + 2 * (size_t)maxcor * ld + 2 * 64 + 4 * 512 + (sizeof(SolverState) + 63) / 64 * 8;
+  const size_t n_dbl = 8 * ld + 2 * (size_t)maxcor * ld + 2 * 64 + 4 * 512 + (sizeof(SolverState) + 63) / 64 * 8;
   MLN_TRY(f->sv_block.alloc_zeroed(ctx, n_dbl, "sv_block"));
   double* p = f->sv_block;
   SolverBuffers& b = f->sv;
@@ -244,6 +314,7 @@ int fit_solver_alloc(mln_fit* f, int maxcor) {
   b.S = p; p += (size_t)maxcor * ld; b.Y = p; p += (size_t)maxcor * ld;
   b.rho = p; p += 64; b.yy = p; p += 64;
   b.c = p; p += ld;
+  b.ua = p; p += ld; b.ga = p; p += ld;
   b.trace = p; p += 4 * 512;
   b.st = (SolverState*)p;
   b.ld = (int64_t)ld;
@@ -371,14 +442,46 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
   // collectives (Gram all-reduce, the sample's global sum) -- so the decision is made ONCE, here, for all ranks: rank 0's
   // cost rule AND every rank able to keep f (one all-reduce of two numbers: rank 0's vote, the count of ranks that cannot).
   const bool keeps_f = f->f_keep[0] && f->f_keep[1] && objective_can_keep_f(f->n, f->n_wg);
+  // The importance tail's own cost rule (rank 0's, like the rebuild's; the phase itself is described below).  A round of the tail
+  // is ~12 list evaluations -- a pass over 1 / tail_frac of the rows plus the 0.16 ms of small launches every evaluation has --
+  // and a selection of ~0.5 ms; what it saves is full evaluations: four at C3 on five data seeds, but only 0 to 2 on 1e6 x 20
+  // mixtures with 2000 landmarks (tools/importance_tail_sweep.py: 45 -> 49-53 ms with the tail forced on).  It is entered where
+  // it pays even if it saves only TWO: 2 pass_s > 12 (pass / tail_frac + 0.16 ms) + 0.5 ms, i.e. a full pass above ~4.4 ms
+  // (C3 on one GPU: 6.3).  MELLON_AMD_IMPORTANCE_TAIL=1 forces it on wherever the rebuild runs, =0 off.
+  double tail_frac = 8.0;
+  if (const char* ev = mln_experiment("MELLON_AMD_TAIL_FRAC")) tail_frac = std::max(1.0, std::atof(ev));
+  double want_tail = (2.0 * pass_s > 12.0 * ((pass_s - 1.4e-4) / tail_frac + 1.6e-4) + 5e-4) ? 1.0 : 0.0;
+  if (const char* ev = mln_experiment("MELLON_AMD_IMPORTANCE_TAIL")) want_tail = std::atoi(ev) != 0 ? 1.0 : 0.0;
+  double n_total = (double)f->n;     // cells of all ranks (the same all-reduce): the importance tail's sample size is a share of it
   {
-    double vote[2] = {ctx->rank == 0 ? want_rebuild : 0.0, keeps_f ? 0.0 : 1.0};
-    MLN_HIP(ctx, hipMemcpyAsync(f->d_tmp, vote, sizeof(vote), hipMemcpyHostToDevice, ctx->stream));
-    MLN_TRY(dev_allreduce(ctx, f->d_tmp, 2));
-    MLN_HIP(ctx, hipMemcpyAsync(vote, f->d_tmp, sizeof(vote), hipMemcpyDeviceToHost, ctx->stream));
+    // (rank 0's two cost rules travel in one number: 1 = rebuild, 2 = importance tail, below)
+    double vote[3] = {ctx->rank == 0 ? want_rebuild + 2.0 * want_tail : 0.0, keeps_f ? 0.0 : 1.0, (double)f->n};
+    MLN_HIP(ctx, hipMemcpyAsync(f->d_out, vote, sizeof(vote), hipMemcpyHostToDevice, ctx->stream));
+    MLN_TRY(dev_allreduce(ctx, f->d_out, 3));
+    MLN_HIP(ctx, hipMemcpyAsync(vote, f->d_out, sizeof(vote), hipMemcpyDeviceToHost, ctx->stream));
     MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    want_rebuild = (vote[0] != 0.0 && vote[1] == 0.0) ? 1.0 : 0.0;
+    want_tail = ((int)vote[0] & 2) ? 1.0 : 0.0;
+    want_rebuild = (((int)vote[0] & 1) && vote[1] == 0.0) ? 1.0 : 0.0;
+    n_total = vote[2];
   }
+  // Importance tail (solver.h): after the FIRST rebuild of a pure-fp64 solve the passes run over an importance-sampled row
+  // list of ~n_total / tail_frac cells, drawn at the pause point by the rebuild's own machinery (same hash of the global cell
+  // index, so the list is the same for every sharding and contains the rebuild's sample), the full objective anchoring and
+  // verifying.  Entered only where the rebuild is (rebuild armed, fp64, every rank keeps f), never in the mixed solve.
+  // MELLON_AMD_IMPORTANCE_TAIL=0: off (the solve then finishes on full passes), 1: on wherever the rebuild runs, unset: the cost
+  // rule above; MELLON_AMD_TAIL_FRAC=<k>: n_total / k rows;
+  // MELLON_AMD_TAIL_FTOL=<x>: the surrogate's relative noise floor (solver.h tail_ftol); MELLON_AMD_TAIL_POOR_LIST=1: tests only, below.
+  // How many rows: n_total / 8, and at least 24 per landmark.  C3, one step, ms (parent 131.8, 12 full passes): n / 8 -> 119.0
+  // (8 full passes, 10 list passes), n / 16 -> 131.7 (11, 11), n / 32 -> 131.2 (11, 14): the point a list of 12 m rows leads to
+  // is 0.03 above the optimum in the loss, that of 25 m rows 0.003 -- one verification more, and each costs a full pass.  At
+  // 40 000 cells x 300 landmarks a list of n / 16 = 8 m rows needed four anchors (14 full passes against the parent's 12).
+  // A list that would be more than half the cells is not worth its evaluations' fixed cost: no tail then.
+  const bool tail_enabled = !phase32 && want_rebuild != 0.0 && want_tail != 0.0;
+  init.tail_max_evals = 24;
+  init.tail_ftol = 100.0 * o.ftol;    // (solver.h: the surrogate's noise floor; measured at C3 with ftol = 1e-13)
+  if (const char* ev = mln_experiment("MELLON_AMD_TAIL_FTOL")) init.tail_ftol = std::atof(ev);
+  if (f->tail_sel.idx || f->tail_sel.scale) { MLN_HIP(ctx, hipStreamSynchronize(ctx->stream)); f->tail_sel.reset(); }
+  const RebuildSelection* tail_live = nullptr;
   // (round 5: up to max_rebuilds of them -- after the first, whenever the solve has fallen back to slow linear convergence,
   //  solver.hip; C3 takes one)
   int max_rebuilds = 1000;    // (rate-limited by the solver's own rules: six iterations apart, only on slow linear convergence)
@@ -426,7 +529,7 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
   for (;;) {
     for (int b = 0; b < batch; ++b) {
       MLN_TRY(launch_solver_step(ctx, f->sv, (int)m));
-      MLN_TRY(fit_enqueue_eval(f, f->sv.un, f->sv.gn, false, gate, events_for(n_enq), subs_live));
+      MLN_TRY(fit_enqueue_eval(f, f->sv.un, f->sv.gn, false, gate, events_for(n_enq), subs_live, tail_live));
       ++n_enq;
     }
     // rank 0's state decides for everyone (it is the same state on every rank by construction: identical inputs,
@@ -475,9 +578,26 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
           // on the tree ran the corrected surrogate to the iteration limit) and goes on with the plain 32-bit surrogate.
           if (revert && ps.corr && (ps.gate_after_pause & 3) == MLN_GATE_F32)
             MLN_TRY(launch_solver_resume_plain32(ctx, f->sv, MLN_GATE_F32, (int)m, 1));
-          else
+          else {
+            // first rebuild of an fp64 solve: draw the importance tail's rows at this point (collective; global quantities
+            // decide, so every rank takes the same branch) and resume on them
+            int resume_gate = ps.gate_after_pause;
+            const double tail_target = std::max(n_total / tail_frac, 24.0 * (double)m);
+            if (tail_enabled && !revert && rebuilds_this_solve == 0 && !tail_live && ps.gate_after_pause == MLN_GATE_F64 && !ps.corr &&
+                tail_target <= 0.5 * n_total) {
+              // (MELLON_AMD_TAIL_POOR_LIST=1, tests only: the list keeps the rebuild's row scales, at most 1, as its weights --
+              //  a surrogate with far too little curvature, whose minimiser is worse on the full objective: the guard's case)
+              const char* poor = mln_experiment("MELLON_AMD_TAIL_POOR_LIST");
+              MLN_TRY(rebuild_select_rows(ctx, f->f_keep[ps.f_slot], f->V, f->n, f->row0, tail_target, 0x6d656c6c6f6eull, &f->tail_sel, ps.cap,
+                                          !(poor && std::atoi(poor) != 0)));
+              tail_live = &f->tail_sel;
+              resume_gate = MLN_GATE_TAIL;
+              if (trace_lvl) fprintf(stderr, "[trace] importance tail: %lld of %lld local rows (target %.0f of %.0f), c = %.4g\n",
+                                     (long long)f->tail_sel.rows, (long long)f->n, tail_target, n_total, f->tail_sel.c);
+            }
             // (the trial applies to the LAST rebuild the solve is allowed: while more remain, a stall leads to the next one)
-            MLN_TRY(launch_solver_resume(ctx, f->sv, ps.gate_after_pause, 1, (revert || ps.rebuild_armed > 0) ? 0 : revert_after));
+            MLN_TRY(launch_solver_resume(ctx, f->sv, resume_gate, 1, (revert || ps.rebuild_armed > 0) ? 0 : revert_after));
+          }
           if (revert) f->n_revert += 1; else { f->n_rebuild += 1; rebuilds_this_solve += 1; }
         } else {
           // the rebuild declined (weights too wild) or lost positive definiteness: same variable, same history, carry on --
@@ -504,6 +624,9 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
     if (batch < 16 && f->h_state->gate == MLN_GATE_F64) batch = std::min(batch, 6);
   }
   const SolverState st = *f->h_state;
+  const int64_t tail_rows = f->tail_sel.rows;
+  if (tail_live) { (void)hipStreamSynchronize(ctx->stream); f->tail_sel.reset(); f->tail_rows = tail_rows; }
+  f->n_tail_guard += st.n_tail_guard;
   if (f->pc_saved.C) (void)hipStreamSynchronize(ctx->stream);
   f->pc_saved = Precond();
   f->n_start_halvings = st.n_shrink;
@@ -515,7 +638,7 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
     MLN_HIP(ctx, hipMemcpy(tr.data(), f->sv.trace, sizeof(double) * 4 * n_done, hipMemcpyDeviceToHost));
     for (int i = 0; i < n_done && timing; ++i) {
       const int gcode = (int)tr[4 * i + 3] & 15, lvl = (int)tr[4 * i + 3] >> 4;
-      const bool was32 = (gcode & 3) == MLN_GATE_F32, was_sub = gcode == MLN_GATE_SUB;
+      const bool was32 = (gcode & 3) == MLN_GATE_F32, was_sub = gcode == MLN_GATE_SUB, was_tail = gcode == MLN_GATE_TAIL;
       int slot = i;
       for (const auto& sh : slot_shift) if (i >= sh.first) slot = i + sh.second;
       if (3 * (slot + 1) > (int)f->evs.size()) continue;
@@ -525,12 +648,16 @@ extern "C" int mln_map_solve(mln_fit* f, const double* z0, const mln_solver_opts
         f->times_sub += 1e-3 * ms; f->evals_sub += 1;
         f->sub_pass_equiv += 1.0 / (double)((lvl >= 0 && lvl < (int)sub_strides.size()) ? sub_strides[lvl] : 1);
       }
+      else if (was_tail) {   // counted like the strided passes: by rows / n, and not among the full-size fp64 launches
+        f->times_tail += 1e-3 * ms; f->evals_tail += 1;
+        f->sub_pass_equiv += f->n > 0 ? (double)tail_rows / (double)f->n : 0.0;
+      }
       else if (was32) { f->times32 += 1e-3 * ms; f->evals32 += 1; }
       else { f->times[5] += 1e-3 * ms; f->times[6] += 1.0; f->times[7] = (double)f->n * (double)f->ldl * 8.0; }
     }
     if (trace_lvl >= 2)
       for (int i = 0; i < n_done; ++i)
-        fprintf(stderr, "[eval %d] %s mode=%d t=%.3g f=%.15g\n", i, ((int)tr[4 * i + 3] & 15) == MLN_GATE_F32 ? "f32" : (((int)tr[4 * i + 3] & 15) == MLN_GATE_F32C ? "f32c" : (((int)tr[4 * i + 3] & 15) == MLN_GATE_SUB ? (((int)tr[4 * i + 3] >> 4) ? "sub1" : "sub0") : "f64")),
+        fprintf(stderr, "[eval %d] %s mode=%d t=%.3g f=%.15g\n", i, ((int)tr[4 * i + 3] & 15) == MLN_GATE_F32 ? "f32" : (((int)tr[4 * i + 3] & 15) == MLN_GATE_F32C ? "f32c" : (((int)tr[4 * i + 3] & 15) == MLN_GATE_SUB ? (((int)tr[4 * i + 3] >> 4) ? "sub1" : "sub0") : (((int)tr[4 * i + 3] & 15) == MLN_GATE_TAIL ? "tail" : "f64"))),
                 (int)tr[4 * i + 2], tr[4 * i + 1], tr[4 * i]);
   }
   // z = C^-T u and w = P u at the accepted point, remembered for transform / predictor weights
@@ -626,6 +753,10 @@ extern "C" int mln_stage_times(mln_fit* f, double* out) {
   out[19] = (double)f->n_revert;                        // second preconditioner failed its trial: first one restored
   out[20] = (double)f->n_start_halvings;                // halvings of a start whose loss was not finite or above 1e30
   out[21] = (double)f->rank_path;                       // mln_fit_gram_rank: 1 = inertia, 2 = tridiagonalisation
+  out[22] = (double)f->evals_tail;                      // importance tail: launches over the row list (not in out[6]; in out[17] by rows / n)
+  out[23] = (double)f->tail_rows;                       //                  rows of this rank's list (last solve)
+  out[24] = f->times_tail;                              //                  kernel seconds
+  out[25] = (double)f->n_tail_guard;                    //                  guard: the full loss rose, back to the anchor, phase off
   return MLN_OK;
 }
 

@@ -30,11 +30,17 @@ struct ObjArgs {
   int64_t seg_cols;       // > 0: L points at a segment of seg_cols columns of a wider matrix (row pitch ldl): m > 8192
   int64_t seg_left;       //      ... and this many (padded) columns remain in the row from that pointer
   int f_accum;            // f_out mode: add this segment's dot products to what f_out already holds
+  const int64_t* rows;    // if non-null (device, n entries): logical row i of the pass is row rows[i] of the buffer and of V / Vdr
+                          //   (row_stride / row_first unused) -- the importance-sampled tail of the solve (solver.hip "tail")
+  const double* row_w;    // with rows, optional (n entries, by list position): factor w_i on row i's exponential,
+                          //   w_i e^{f_i + V_i} - (f_i + Vdr_i)  (objective.hip "row LIST")
 };
 // (the objective kernels compare gate & 3 with gate_want: MLN_GATE_F32C streams the same copy as MLN_GATE_F32;
 //  MLN_GATE_SUB selects the launch over the row subsample; MLN_GATE_PAUSE, like DONE, stops every launch of the chain
-//  until the host has rebuilt the preconditioner and resumed the solver)
-enum { MLN_GATE_F64 = 0, MLN_GATE_F32 = 1, MLN_GATE_DONE = 2, MLN_GATE_SUB = 3, MLN_GATE_F32C = 5, MLN_GATE_PAUSE = 6 };
+//  until the host has rebuilt the preconditioner and resumed the solver; MLN_GATE_TAIL selects, like SUB, a launch over a
+//  row subset -- the one whose gate2_want is MLN_TAIL_LEVEL, which the solver's sub_level holds while that phase runs)
+enum { MLN_GATE_F64 = 0, MLN_GATE_F32 = 1, MLN_GATE_DONE = 2, MLN_GATE_SUB = 3, MLN_GATE_F32C = 5, MLN_GATE_PAUSE = 6, MLN_GATE_TAIL = 7 };
+enum { MLN_TAIL_LEVEL = 64 };
 int objective_max_m();
 int objective_max_m_one_pass();   // beyond it the pass is segmented (launch_objective_wide): no row map, no device-resident solver
 bool objective_can_keep_f(int64_t n, int n_wg);

@@ -63,6 +63,61 @@ __device__ __forceinline__ void load_rows(const d2* __restrict__ L2, int64_t ld2
   }
 }
 
+// ---- row LIST (ObjArgs::rows): the importance-sampled tail of the solve -------------------------------------------
+// Logical row i of the pass is row rows[i] of the buffer; V / Vdr are indexed by rows[i], the weight row_w by i.  Each
+// row is still ~8 ld contiguous bytes, so the pass streams at the rate of the strided one -- nothing is gathered.
+// The weight is a factor on the row's EXPONENTIAL:  w_i e^{f_i + V_i} - (f_i + Vdr_i),  derivative w_i e^{f_i + V_i} - 1
+// (the same function as log w_i folded into V_i, except that the cap still tests t = f + V, so it means what it means in
+// the full pass).  The -f_i term stays unweighted on purpose: it is linear in u, so the sum over the list is off from the
+// sum over all cells by something linear in u, which the solver's anchor correction (solver.hip "tail") cancels EXACTLY --
+// while weighting it by 1 / p_i, up to thousands, multiplied the rounding error of every f_i into the loss (measured at C3:
+// 2e-5 of evaluation noise on a loss of 5.4e6, forty times the stopping tolerance; the line searches never ended).  What is
+// sampled is sum_i e^{f_i + V_i}, in proportion to its terms.  A list without weights multiplies by exactly 1: an arithmetic
+// progression then gives the bits of the strided launch over the same rows.
+// The list entries of a step are wave-uniform (scalar loads) and are requested ONE HALF-ITERATION before the row loads
+// that need them as addresses -- behind a whole process_rows -- so the row loads never wait for a dependent load.
+template <int R>
+__device__ __forceinline__ void load_idx(const ObjArgs& a, int64_t row, int64_t (&idx)[R]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) idx[r] = a.rows[(row + r < a.n) ? (row + r) : (a.n - 1)];   // (past the end: coefficient 0)
+}
+
+template <int CPT, int R>
+__device__ __forceinline__ void load_rows_idx(const d2* __restrict__ L2, int64_t ld2, const int64_t (&idx)[R], unsigned tid,
+                                              d2 (&v)[R][CPT], unsigned lim) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const d2* rowp = L2 + idx[r] * ld2;
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {   // unconditional, clamped: see load_rows
+      unsigned off = (unsigned)c * WG + tid;
+      off = (off < lim) ? off : lim - 1u;
+      v[r][c] = __builtin_nontemporal_load(rowp + off);
+    }
+  }
+}
+
+template <int R, bool VEC>
+__device__ __forceinline__ void load_lik_idx(const ObjArgs& a, int64_t row, const int64_t (&idx)[R], int tid, double (&pv)[3][R]) {
+  if constexpr (VEC) {   // lane l < R owns row l of the step (load_lik_vec)
+    const int lane = tid & 63;
+    int64_t i = idx[R - 1];
+#pragma unroll
+    for (int r = 0; r < R - 1; ++r) i = (lane == r) ? idx[r] : i;
+    const int64_t want = row + (lane < R ? lane : R - 1);
+    pv[0][0] = a.V[i];
+    pv[1][0] = a.Vdr[i];
+    pv[2][0] = a.row_w ? a.row_w[(want < a.n) ? want : (a.n - 1)] : 1.0;
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      pv[0][r] = a.V[idx[r]];
+      pv[1][r] = a.Vdr[idx[r]];
+      pv[2][r] = a.row_w ? a.row_w[(row + r < a.n) ? (row + r) : (a.n - 1)] : 1.0;
+    }
+  }
+}
+
 // V and Vdr of the R rows of a step (clamped to the last row: rows past the end have coefficient 0)
 // lds_barrier_unused: the per-step barrier only publishes eight partial dot products through LDS, so
 // "s_waitcnt lgkmcnt(0); s_barrier" would do, and it would leave the prefetched rows of the next step in flight where
@@ -72,7 +127,7 @@ __device__ __forceinline__ void load_rows(const d2* __restrict__ L2, int64_t ld2
 // are revisited.  The full fence stays.
 
 template <int R>
-__device__ __forceinline__ void load_lik(const ObjArgs& a, int64_t row, double (&pv)[2][R]) {
+__device__ __forceinline__ void load_lik(const ObjArgs& a, int64_t row, double (&pv)[3][R]) {
   const RowMap rm = row_map(a);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -85,7 +140,7 @@ __device__ __forceinline__ void load_lik(const ObjArgs& a, int64_t row, double (
 // VEC variants (few column pairs per thread: m <= 3072): lane l < R owns row l of the step -- its V / Vdr arrive as ONE
 // vector load per lane instead of R wave-uniform ones
 template <int R>
-__device__ __forceinline__ void load_lik_vec(const ObjArgs& a, int64_t row, int tid, double (&pv)[2][R]) {
+__device__ __forceinline__ void load_lik_vec(const ObjArgs& a, int64_t row, int tid, double (&pv)[3][R]) {
   const RowMap rm = row_map(a);
   const int lane = tid & 63;
   const int64_t want = row + (lane < R ? lane : R - 1);
@@ -124,11 +179,12 @@ __device__ __forceinline__ double transposed_wave_sum(double (&v)[R], int lane) 
   return s;
 }
 
-template <int CPT, int R, int MODE, bool KEEP, bool VEC = false>
+template <int CPT, int R, int MODE, bool KEEP, bool VEC = false, bool LIST = false>
 __device__ __forceinline__ void process_rows(const ObjArgs& a, int64_t row, int64_t row_end, int tid, int par,
                                              const d2 (&v)[R][CPT], const d2 (&z)[CPT], d2 (&g)[CPT],
                                              d2 (&h)[CPT], double& loss, double (*red)[8][R], double* fstage,
-                                             int64_t fbase, const double (&pv)[2][R], const double capv, int& any_over) {
+                                             int64_t fbase, const double (&pv)[3][R], const double capv, int& any_over) {
+  // (pv[2]: the row's weight -- LIST launches only, see load_idx)
   // capv (+inf unless the solver's cap is on): beyond t = capv, e^t is continued by its second-order Taylor polynomial there --
   // e^cap (1 + d + d^2 / 2), d = t - cap: a convex C^2 minorant with curvature bounded by e^cap, identical to e^t wherever no
   // row is above the cap (solver.hip "capped start"; round 5: quadratic instead of linear, and in the fp64 / subsample passes too)
@@ -168,7 +224,8 @@ __device__ __forceinline__ void process_rows(const ObjArgs& a, int64_t row, int6
     const double Vi = pv[0][0];                       // (this lane's row: load_lik_vec)
     const double tt = f + Vi;
     const bool over = tt > capv;
-    const double ex = rok ? exp(over ? capv : tt) : 0.0;
+    double ex = rok ? exp(over ? capv : tt) : 0.0;
+    if constexpr (LIST) ex *= pv[2][0];               // (the row's weight: see load_idx)
     const double dc = over ? (tt - capv) : 0.0;
     const double e = ex * fma(dc, fma(0.5, dc, 1.0), 1.0);
     const double cf = rok ? (over ? fma(ex, dc, ex - 1.0) : ex - 1.0) : 0.0;
@@ -215,15 +272,16 @@ __device__ __forceinline__ void process_rows(const ObjArgs& a, int64_t row, int6
       } else {
         // KEEP: V / Vdr of the row were requested together with the row itself (load_lik) -- a load issued HERE would
         // sit behind the next set's row loads in the in-order return queue (s_waitcnt vmcnt(0))
-        const double Vi = KEEP ? pv[0][r] : (rok ? a.V[rm(row + r)] : 0.0);
+        const double Vi = (KEEP || LIST) ? pv[0][r] : (rok ? a.V[rm(row + r)] : 0.0);
         const double tt = f + Vi;
         const bool over = tt > capv;
-        const double ex = rok ? exp(over ? capv : tt) : 0.0;
+        double ex = rok ? exp(over ? capv : tt) : 0.0;
+        if constexpr (LIST) ex *= pv[2][r];           // (the row's weight: see load_idx)
         const double dc = over ? (tt - capv) : 0.0;
         const double e = ex * fma(dc, fma(0.5, dc, 1.0), 1.0);
         aexp[r] = ex;
         coef[r] = rok ? (over ? fma(ex, dc, ex - 1.0) : ex - 1.0) : 0.0;
-        if (KEEP) { if (tid == 0 && rok) loss -= (f + pv[1][r]) - e; }
+        if (KEEP || LIST) { if (tid == 0 && rok) loss -= (f + pv[1][r]) - e; }
         else if (tid == 0 && rok) loss -= (f + a.Vdr[rm(row + r)]) - e;   // inference.py:89-91
         any_over += (tid == 0 && rok && over) ? 1 : 0;
         // f of the row goes to LDS.  Unconditional store by every lane (thread 0 to the row's slot, the others to a
@@ -249,7 +307,7 @@ __device__ __forceinline__ void process_rows(const ObjArgs& a, int64_t row, int6
   }
 }
 
-template <int CPT, int R, int MODE, bool KEEP = false, bool VEC = false>
+template <int CPT, int R, int MODE, bool KEEP = false, bool VEC = false, bool LIST = false>
 __global__ __launch_bounds__(WG) void k_objective(ObjArgs a) {
   if (a.gate && (*a.gate & 3) != a.gate_want) return;   // uniform: the device-resident solver chose the other copy / is done
   if (a.gate2 && *a.gate2 != a.gate2_want) return;      //          ... or another subsample level
@@ -287,11 +345,32 @@ __global__ __launch_bounds__(WG) void k_objective(ObjArgs a) {
   // count between any use and the loads it depends on is then static, so the compiler waits with
   // vmcnt(loads of one set) instead of vmcnt(0) and one set is always in flight behind the one consumed.
   const int64_t s_last = s_end - 1;
-  double pa[2][R], pb[2][R];
+  double pa[3][R], pb[3][R];
   const RowMap rm = row_map(a);
   const unsigned lim = a.seg_cols > 0 ? (unsigned)(a.seg_left / 2) : (unsigned)ld2;
-  auto lik = [&](int64_t r0, double (&pv)[2][R]) { if (VEC) load_lik_vec<R>(a, r0, tid, pv); else load_lik<R>(a, r0, pv); };
+  auto lik = [&](int64_t r0, double (&pv)[3][R]) { if (VEC) load_lik_vec<R>(a, r0, tid, pv); else load_lik<R>(a, r0, pv); };
   constexpr bool PRE = KEEP || (VEC && (MODE == MODE_OBJ || MODE == MODE_OBJ_HESS));   // V / Vdr travel with the rows (a per-lane load after the barrier would drain the prefetch)
+  if constexpr (LIST) {
+    // the same pipeline over a row list: the entries of the set loaded NEXT are already in registers (load_idx)
+    int64_t ia[R], ib[R];
+    if (s_beg < s_end) {
+      load_idx<R>(a, s_beg * R, ia);
+      load_idx<R>(a, ((s_beg + 1 < s_end) ? s_beg + 1 : s_last) * R, ib);
+      load_rows_idx<CPT, R>(L2, ld2, ia, tid, va, lim);
+      load_lik_idx<R, VEC>(a, s_beg * R, ia, tid, pa);
+    }
+    for (int64_t s = s_beg; s < s_end; s += 2) {
+      const int64_t s1 = (s + 1 < s_end) ? s + 1 : s_last, s2 = (s + 2 < s_end) ? s + 2 : s_last, s3 = (s + 3 < s_end) ? s + 3 : s_last;
+      load_rows_idx<CPT, R>(L2, ld2, ib, tid, vb, lim);
+      load_lik_idx<R, VEC>(a, s1 * R, ib, tid, pb);
+      load_idx<R>(a, s2 * R, ia);
+      process_rows<CPT, R, MODE, KEEP, VEC, true>(a, s * R, a.n, tid, 0, va, z, g, h, loss, red, fstage, fbase, pa, capv, any_over);
+      load_rows_idx<CPT, R>(L2, ld2, ia, tid, va, lim);
+      load_lik_idx<R, VEC>(a, s2 * R, ia, tid, pa);
+      load_idx<R>(a, s3 * R, ib);
+      if (s + 1 < s_end) process_rows<CPT, R, MODE, KEEP, VEC, true>(a, (s + 1) * R, a.n, tid, 1, vb, z, g, h, loss, red, fstage, fbase, pb, capv, any_over);
+    }
+  } else {
   if (s_beg < s_end) { load_rows<CPT, R>(L2, ld2, s_beg * R, a.n, tid, va, rm, lim); if (PRE) lik(s_beg * R, pa); }
   for (int64_t s = s_beg; s < s_end; s += 2) {
     const int64_t s1 = (s + 1 < s_end) ? s + 1 : s_last, s2 = (s + 2 < s_end) ? s + 2 : s_last;
@@ -301,6 +380,7 @@ __global__ __launch_bounds__(WG) void k_objective(ObjArgs a) {
     load_rows<CPT, R>(L2, ld2, s2 * R, a.n, tid, va, rm, lim);
     if (PRE) lik(s2 * R, pa);
     if (s + 1 < s_end) process_rows<CPT, R, MODE, KEEP, VEC>(a, (s + 1) * R, a.n, tid, 1, vb, z, g, h, loss, red, fstage, fbase, pb, capv, any_over);
+  }
   }
   if (any_over && a.over_flag) atomicAdd(a.over_flag, any_over);      // (integer count: the order of the adds does not matter)
   if (KEEP) {
@@ -369,7 +449,7 @@ template <int CQ, int R, bool GEMVT, bool KEEP, int NW, bool FIXED, bool VEC = f
 __device__ __forceinline__ void process_rows32(const ObjArgs& a, int64_t row, int64_t row_end, int tid, int par,
                                                const f4 (&v)[R][CQ], const double (&z)[CQ][4], double (&g)[CQ][4],
                                                double& loss, double (*red)[NW][R], double* fstage, int64_t fbase,
-                                               const double (&pv)[2][R], double capv, double ecap, int& any_over) {
+                                               const double (&pv)[3][R], double capv, double ecap, int& any_over) {
   double coef[R], dot[R];
   const RowMap rm = row_map(a);
   if (GEMVT) {   // grad_j = sum_i weights_i L_ij  (Ridge right-hand side): no row dots, no barrier
@@ -509,10 +589,10 @@ __global__ __launch_bounds__(64 * NW) void k_objective32(ObjArgs a) {
   const int64_t fbase = s_beg * R;
   f4 va[R][CQ], vb[R][CQ];
   const int64_t s_last = s_end - 1;
-  double pa[2][R], pb[2][R];
+  double pa[3][R], pb[3][R];
   const RowMap rm = row_map(a);
   constexpr bool PRE = KEEP || (VEC && !GEMVT);
-  auto lik = [&](int64_t r0, double (&pv)[2][R]) { if (VEC) load_lik_vec<R>(a, r0, tid, pv); else load_lik<R>(a, r0, pv); };
+  auto lik = [&](int64_t r0, double (&pv)[3][R]) { if (VEC) load_lik_vec<R>(a, r0, tid, pv); else load_lik<R>(a, r0, pv); };
   if (s_beg < s_end) { load_rows32<CQ, R, NW>(L4, ld4, s_beg * R, a.n, tid, va, rm); if (PRE) lik(s_beg * R, pa); }
   for (int64_t s = s_beg; s < s_end; s += 2) {   // unconditional loads: see k_objective
     const int64_t s1 = (s + 1 < s_end) ? s + 1 : s_last, s2 = (s + 2 < s_end) ? s + 2 : s_last;
@@ -713,7 +793,9 @@ int launch_mode(mln_ctx* ctx, const ObjArgs& a, int mode) {
   dim3 grid((unsigned)a.n_wg), block(WG);
   switch (mode) {
     case MODE_OBJ:
-      if (a.f_slot) hipLaunchKernelGGL((k_objective<CPT, R, MODE_OBJ, true, VEC>), grid, block, 0, ctx->stream, a);
+      if (a.rows && a.f_slot) hipLaunchKernelGGL((k_objective<CPT, R, MODE_OBJ, true, VEC, true>), grid, block, 0, ctx->stream, a);
+      else if (a.rows) hipLaunchKernelGGL((k_objective<CPT, R, MODE_OBJ, false, VEC, true>), grid, block, 0, ctx->stream, a);
+      else if (a.f_slot) hipLaunchKernelGGL((k_objective<CPT, R, MODE_OBJ, true, VEC>), grid, block, 0, ctx->stream, a);
       else hipLaunchKernelGGL((k_objective<CPT, R, MODE_OBJ, false, VEC>), grid, block, 0, ctx->stream, a);
       break;
     case MODE_OBJ_HESS: hipLaunchKernelGGL((k_objective<CPT, R, MODE_OBJ_HESS, false, VEC>), grid, block, 0, ctx->stream, a); break;
@@ -768,7 +850,7 @@ int launch_objective(mln_ctx* ctx, const ObjArgs& a);
 // segments: two reads of the buffer instead of one.  Host-driven evaluations only (no device-resident solver, no
 // 32-bit copy, no Hessian diagonal).
 static int launch_objective_wide(mln_ctx* ctx, const ObjArgs& a) {
-  if (a.gate || a.part_hess || a.L32 || (a.row_stride > 1)) {
+  if (a.gate || a.part_hess || a.L32 || (a.row_stride > 1) || a.rows) {
     mln_set_error(ctx, "objective: this mode is not available beyond 8192 landmarks");
     return MLN_ERR_UNSUPPORTED;
   }
@@ -824,6 +906,10 @@ int launch_objective(mln_ctx* ctx, const ObjArgs& a) {
   if (a.weights) mode = MODE_GEMVT;
   else if (a.f_out) mode = MODE_FONLY;
   else if (a.part_hess) mode = MODE_OBJ_HESS;
+  if (a.rows && (mode != MODE_OBJ || a.L32 || a.seg_cols > 0)) {
+    mln_set_error(ctx, "objective: a row list goes with the plain fp64 objective only");
+    return MLN_ERR_UNSUPPORTED;
+  }
   if (a.L32 && (mode == MODE_OBJ || mode == MODE_GEMVT) && a.ldl % 4 == 0) {   // fp32 copy: 4 columns per 16-byte lane load
     const int cq = (int)((a.ldl / 4 + WG - 1) / WG);
     const bool vec32 = mode == MODE_OBJ;

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void k_select_count(const double* __restrict__
 // ... and their indices (ascending) and scales sqrt(w_i / w_max), w_i = max(a_i, 1 / c): one wave per block keeps order
 __global__ __launch_bounds__(64) void k_select_write(const double* __restrict__ a, int64_t n, double c, int64_t row0,
                                                      uint64_t seed, const int64_t* __restrict__ offsets, double inv_wmax,
-                                                     int64_t* __restrict__ idx, double* __restrict__ scale) {
+                                                     int64_t* __restrict__ idx, double* __restrict__ scale, int inverse_prob) {
   const int64_t base = (int64_t)blockIdx.x * SB;
   int64_t out = offsets[blockIdx.x];
   for (int j0 = 0; j0 < SB; j0 += 64) {
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64) void k_select_write(const double* __restrict__ 
       const int pos = __popcll(mask & ((1ull << threadIdx.x) - 1ull));
       idx[out + pos] = i;
       const double w = fmax(a[i], 1.0 / c);
-      scale[out + pos] = sqrt(w * inv_wmax);
+      scale[out + pos] = inverse_prob ? fmax(1.0, 1.0 / (c * a[i])) : sqrt(w * inv_wmax);
     }
     out += __popcll(mask);
   }
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void k_gather_scale(const double* __restrict__
 }  // namespace
 
 int rebuild_select_rows(mln_ctx* ctx, const double* f_dev, const double* V_dev, int64_t n, int64_t row0,
-                        double target_rows_global, uint64_t seed, RebuildSelection* out, double cap) {
+                        double target_rows_global, uint64_t seed, RebuildSelection* out, double cap, bool inverse_prob) {
   *out = RebuildSelection();
   const int nb = 256;
   DevBuf<double> a, part, part2, scal;
@@ -239,7 +239,7 @@ int rebuild_select_rows(mln_ctx* ctx, const double* f_dev, const double* V_dev, 
         rc = MLN_ERR_HIP;
       if (rc == MLN_OK) {
         hipLaunchKernelGGL(k_select_write, dim3((unsigned)n_blk), dim3(64), 0, ctx->stream, a.get(), n, c, row0, seed, offsets.get(),
-                           1.0 / w_max, out->idx.get(), out->scale.get());
+                           1.0 / w_max, out->idx.get(), out->scale.get(), inverse_prob ? 1 : 0);
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = MLN_ERR_HIP;
       }
     }

@@ -78,6 +78,25 @@ struct SolverState {
   int revert_after;
   int it_at_resume;         // -1: not armed
   int pause_reason;         // 1 rebuild, 2 revert
+  // Importance tail (gate == MLN_GATE_TAIL, solver.hip "tail").  After the rebuild the solve finishes on
+  //     F^(u) = F_S(u) + c . u + corr_k,
+  // F_S the weighted objective of an importance-sampled row list (drawn by the host at the pause point with p_i ~ a_i, weights
+  // 1 / p_i), anchored at the point u_a of the last full fp64 pass: F^ and grad F^ equal F and grad F there.  The sampling
+  // error of every term LINEAR in u -- the -f_i of the likelihood -- is cancelled exactly by c; what is left is that of
+  // sum_i a_i(u), sampled in proportion to a_i.  The full objective verifies and re-anchors as in phase C.
+  int tail_on;              // the phase is in force (set by the resume that enters it; cleared by the guard / after four anchors)
+  int tail_sync;            // the evaluation in flight is F_S at the accepted point, whose fx / g are the full pass's: it yields c, corr_k
+  int tail_max_evals;       // evaluations on F^ per anchor after which the full objective is asked anyway
+  int n_eval_anchor;        // ... so far since the last anchor
+  int tail_conv;            // the round of the tail that just ended did so on its own stopping tests (not cut short)
+  int n_tail_guard;         // verification passes that found the full loss ABOVE the previous anchor's: back to that anchor, phase off
+  int tail_over_a;          // over_acc at the last anchor
+  // Relative noise floor of F^.  Its linear part c . u stands for the -f_i of a million rows as ONE dot product of m terms
+  // that cancel (each ~1e9 at C3 against a sum of ~5e7), where the full pass sums a million accurate f_i: evaluations of F^ at
+  // one point scatter by ~5e-5 on a loss of 5.4e6 (1e-11), a hundred times the full objective's.  F^ is asked for nothing
+  // finer: below it the full objective verifies, and once the full gradient promises less than that, full passes finish.
+  double tail_ftol;
+  double tail_fa;           // full loss at the last anchor (its point and gradient: SolverBuffers ua, ga)
 };
 
 struct SolverBuffers {
@@ -86,6 +105,7 @@ struct SolverBuffers {
   double *S, *Y;                 // maxcor x ld
   double *rho, *yy;              // maxcor each: 1 / s.y and y.y
   double* c;                     // m: gradient of (fp64 objective - 32-bit surrogate) at the last anchor
+  double *ua, *ga;               // m each: point and full-objective gradient of the importance tail's last anchor
   const double* z;               // z = C^-T un of the evaluation in flight (m): the prior is 1/2 |z|^2 ...
   const double* z2;              // ... or, when given, 1/2 z . z2  (implicit mode: z = w, z2 = Kj w: 1/2 w^T Kj w = 1/2 |Lp^T w|^2)
   const double* lik;             // its (all-reduced) likelihood sum
@@ -101,6 +121,8 @@ int launch_solver_step(mln_ctx* ctx, const SolverBuffers& b, int m);
 // after a pause: the host has written the accepted point and its gradient in the (new) preconditioned variable into
 // b.u / b.g; the next step starts a line search from there on `gate` (pairs_dropped: the history starts over)
 // rearm >= 0: the number of rebuilds still allowed becomes that (a rebuild that declined twice is not asked for again)
+// gate == MLN_GATE_TAIL enters the importance tail at that point (u / g / fx are those of the pause's full pass): the next
+// step asks for one evaluation of the row list's objective there, the one after it anchors the correction and searches
 int launch_solver_resume(mln_ctx* ctx, const SolverBuffers& b, int gate, int pairs_dropped, int revert_after = 0, int rearm = -1);
 // after a pause at the mixed solve's early fp64 anchor whose rebuild was declined: forget the anchor (it was taken far from
 // the optimum, where the 32-bit surrogate and the fp64 objective differ by more than a first-order correction mends) and

@@ -103,8 +103,15 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
   const bool resume = st->mode == MLN_SOLVE_RESUME;   // the host re-expressed u, g in a new preconditioned variable: no evaluation to consume
   const bool phaseA = st->gate == MLN_GATE_F32, phaseC = st->gate == MLN_GATE_F32C, phaseS = st->gate == MLN_GATE_SUB;
   const bool phase32 = phaseA || phaseC;
-  const bool approx = phase32 || phaseS;               // the evaluation in flight was of a surrogate (32-bit copy / row subsample)
-  if (phaseC) {
+  // Importance tail (solver.h).  phaseT: the evaluation in flight was of the row list's objective F_S -- corrected like
+  // phase C's, F^ = F_S + c . u + k, except for the ONE evaluation at the pause point (tail_sync) that defines c and k from
+  // the full pass's loss and gradient there.  The rules that end phase C on its surrogate and let the fp64 objective
+  // verify, re-anchor (at most four times) or stop apply to F^ as they stand (phaseCT).
+  const bool phaseT = st->gate == MLN_GATE_TAIL;
+  const bool tail_sync = phaseT && !resume && st->tail_sync != 0;
+  const bool phaseCT = phaseC || phaseT;
+  const bool approx = phase32 || phaseS || phaseT;     // the evaluation in flight was of a surrogate (32-bit copy / row subsample / row list)
+  if (phaseC || (phaseT && !resume && !tail_sync)) {
     double cu = 0.0;
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
@@ -122,7 +129,12 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
   double dec_prev = st->dec_prev, dec_prev2 = st->dec_prev2;
   const bool after_switch = mode == MLN_SOLVE_REEVAL && !phaseS && !phaseC && st->n_eval_sub > 0 && st->it_full == 0;   // (full objective, first direction)
   bool recap = false;
-  if (mode != MLN_SOLVE_LS && !resume) t0 = 1.0;
+  if (mode != MLN_SOLVE_LS && !resume && !tail_sync) t0 = 1.0;
+  int tail_on = st->tail_on, n_eval_anchor = st->n_eval_anchor + ((phaseT && !resume && !tail_sync) ? 1 : 0);
+  bool tail_cut = false;   // this round of the tail ends because F^ was given up on, not because it converged
+  int n_tail_guard = st->n_tail_guard, tail_over_a = st->tail_over_a;
+  double tail_fa = st->tail_fa;
+  bool tail_req = false, tail_back = false, new_anchor = false;
   int f_slot = st->f_slot, f_valid = st->f_valid, corr = st->corr, n_anchor = st->n_anchor;
   int over_acc = st->over_acc;
   double over_cnt_acc = st->over_cnt_acc;
@@ -135,16 +147,53 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
   bool to_head = false, reeval = false, done = false, verify = false, pause = false, shrink = false;
   int pause_reason = 1;
   if (resume) {
-    to_head = true;                      // u, g, fx are the accepted point (in the NEW variable when the history was dropped)
     if (!st->resume_keep_pairs) { k = 0; head = 0; }
     dec_prev = 0.0; dec_prev2 = 0.0;
+    // u, g, fx are the accepted point (in the NEW variable when the history was dropped): search from there -- or, entering
+    // the importance tail, first ask for the row list's objective at this very point
+    if (phaseT) tail_req = true; else to_head = true;
   } else if (mode == MLN_SOLVE_FIRST && (!isfinite(fn) || fn > st->start_cap) && st->n_shrink < 64) {
     // pathological start (solver.h: start_cap): same gate, same mode, half the point
 #pragma unroll
     for (int e = 0; e < EPT; ++e) { u[e] *= 0.5; un[e] = u[e]; }
     shrink = true;
+  } else if (tail_sync) {
+    // F_S at the pause point u_a, where fx and g are the full pass's:  c = grad F - grad F_S,  k = F - F_S - c . u_a.
+    // The accepted point, its loss, gradient and rows' f stay the full pass's (f_valid): nothing is accepted here.
+    double cu = 0.0;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+      const double cv = g[e] - gn[e];
+      if (on[e]) b.c[idx[e]] = cv;
+      cu = fma(cv, u[e], cu);
+    }
+    cu = block_sum(cu, red);
+    corr_k = (fx - fn) - cu;
+    corr = 1; n_anchor = 1; n_eval_anchor = 0;
+    to_head = true;
+  } else if (mode == MLN_SOLVE_REEVAL && !approx && tail_on && !(fn <= tail_fa)) {
+    // Guard: the point F^ led to is WORSE on the full objective than the anchor it started from (or not finite) -- the row
+    // list does not describe this problem.  Back to that anchor (its rows' f still sit in f_slot: the verification pass
+    // wrote the other buffer), fresh pairs, and the rest of the solve runs on the full objective.
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) { u[e] = on[e] ? b.ua[idx[e]] : 0.0; g[e] = on[e] ? b.ga[idx[e]] : 0.0; }
+    fx = tail_fa; over_acc = tail_over_a; over_cnt_acc = 0.0;
+    tail_on = 0; corr = 0; ++n_tail_guard;
+    k = 0; head = 0; dec_prev = 0.0; dec_prev2 = 0.0;
+    f_valid = 1;
+    gate = MLN_GATE_F64;
+    tail_back = true;
+    to_head = true;
   } else if (mode != MLN_SOLVE_LS) {            // first point, or the same point again on the fp64 buffer
-    if (mode == MLN_SOLVE_REEVAL && !phase32 && st->use_corr) {
+    const bool tail_verify = mode == MLN_SOLVE_REEVAL && !approx && tail_on;
+    // Two verified points in a row: the full objective fell by no more than ftol |F| over a whole round of the tail (it did
+    // not rise: the guard above) -- SciPy's relative-decrease test with the round as the iteration, on full-pass values.
+    // (Without it the end hung on the predicted decrease g . d below, whose d comes from pairs collected at F^'s noise floor:
+    //  at 40 000 x 300 the loss stood still to 1e-9 over two more anchors and four full passes of line search in the noise.)
+    // (only after a round that ENDED ON ITS OWN stopping tests -- decrease at the noise floor, estimated gap, gradient: a round
+    //  given up on after rejected trials or at its evaluation limit says nothing about convergence, and the rules below go on)
+    if (tail_verify && st->tail_conv && (tail_fa - fn) <= st->ftol * fmax(fmax(fabs(tail_fa), fabs(fn)), 1.0)) { status = 0; done = true; }
+    if ((mode == MLN_SOLVE_REEVAL && !phase32 && st->use_corr) || tail_verify) {
       // fp64 evaluation at the accepted point u, where fx / g hold the surrogate's loss / gradient (F32 after phase A,
       // F^ after phase C): (re)anchor the correction here -- and, after phase C, let the fp64 gradient decide below
       // whether the solve is over (`verify`)
@@ -161,20 +210,31 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
         dcu = block_sum(dcu, red);
         corr_k = (corr ? corr_k : 0.0) + (fn - fx) - dcu;
         corr = 1; ++n_anchor;
-        gate = MLN_GATE_F32C;
+        gate = tail_verify ? MLN_GATE_TAIL : MLN_GATE_F32C;
+        new_anchor = tail_verify;
       } else {
         corr = 0;                                          // four anchors were not enough: finish on the fp64 buffer
+        tail_on = 0;
       }
     }
     fx = fn;
+    if (tail_verify) { dec_prev = 0.0; dec_prev2 = 0.0; }   // (decreases of F^ say nothing about the full objective's rate: the
+                                                            //  "another rebuild" rule and the gap estimate start over)
     over_acc = over_now; over_cnt_acc = over_cnt_now;
-    f_slot ^= 1; f_valid = approx ? 0 : 1;   // the rows' f of this pass belong to the accepted point
+    if (!phaseT) f_slot ^= 1;                // the rows' f of this pass belong to the accepted point (a row-list pass keeps none,
+    f_valid = approx ? 0 : 1;                //  and leaves the last full pass's f where it is: the guard may come back to it)
 #pragma unroll
     for (int e = 0; e < EPT; ++e) g[e] = gn[e];
+    if (new_anchor) {
+#pragma unroll
+      for (int e = 0; e < EPT; ++e)
+        if (on[e]) { b.ua[idx[e]] = u[e]; b.ga[idx[e]] = g[e]; }
+      tail_fa = fx; tail_over_a = over_acc; n_eval_anchor = 0;
+    }
     // first full fp64 evaluation after the subsample levels: the weights a = e^{f+V} of EVERY cell are on the table and the
     // point is close to the optimum -- the moment for the second preconditioner
     if (mode == MLN_SOLVE_REEVAL && !approx && st->rebuild_armed && corr && n_anchor == 1 && st->use_corr) pause = true;   // the early anchor of the mixed solve
-    else to_head = true;
+    else if (!done) to_head = true;
   } else {
     ++ls;
     const bool ok = isfinite(fn) && fn <= fx + 1e-4 * t * gd;
@@ -208,7 +268,8 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
       for (int e = 0; e < EPT; ++e) { u[e] = un[e]; g[e] = gn[e]; }
       fx = fn;
       over_acc = over_now; over_cnt_acc = over_cnt_now;
-      f_slot ^= 1; f_valid = approx ? 0 : 1;
+      if (!phaseT) f_slot ^= 1;
+      f_valid = approx ? 0 : 1;
       if (!phaseS) ++it_full;
       if (sy > 1e-10 * sqrt(ss * yy)) {   // keep the pair (SPD update)
         int slot;
@@ -239,6 +300,16 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
                           (f_old - fx) > st->ftol * fscale;
       if (revert) {
         pause = true; pause_reason = 2;          // (solver.h: revert_after) the host restores the first preconditioner
+        if (phaseT) {
+          // The trial counts the tail's iterations like any others.  The host re-expresses a point of the FULL objective in
+          // the old variable, so the solve goes back to the tail's last anchor (as the guard does: loss, gradient and the
+          // rows' f of a full pass) and the tail, built around the preconditioner that failed, ends with it.
+#pragma unroll
+          for (int e = 0; e < EPT; ++e) { u[e] = on[e] ? b.ua[idx[e]] : 0.0; g[e] = on[e] ? b.ga[idx[e]] : 0.0; }
+          fx = tail_fa; over_acc = tail_over_a; over_cnt_acc = 0.0;
+          tail_on = 0; corr = 0; f_valid = 1;
+          gate = MLN_GATE_F64;
+        }
       } else if (phaseS) {
         // the subsample objective has done its job once its own progress per iteration is small: same point, full objective
         // (not before a few iterations: the very first step from the Ridge start is a cautious t = 1 / |g|_1)
@@ -259,8 +330,8 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
         // relative loss from the true one: once its progress per iteration falls below ftol32, evaluate in fp64 at
         // the same point and continue (corrected surrogate, or the fp64 buffer) with the pairs collected so far
         if ((f_old - fx) <= st->ftol32 * fscale) reeval = true; else to_head = true;
-      } else if ((f_old - fx) <= st->ftol * fscale) {
-        if (phaseC) reeval = true; else { status = 0; done = true; }   // phase C: the fp64 objective has the last word
+      } else if ((f_old - fx) <= (phaseT ? st->tail_ftol : st->ftol) * fscale) {
+        if (phaseCT) reeval = true; else { status = 0; done = true; }   // phase C / tail: the fp64 objective has the last word
       } else {
         const double dec = f_old - fx;
         bool small_gap = false;
@@ -272,21 +343,40 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
           const double r = dec / dec_prev;
           small_gap = dec * r / (1.0 - r) <= st->gap_tol * fscale;
         }
-        if (small_gap) { if (phaseC) reeval = true; else { status = 0; done = true; } }
+        if (small_gap) { if (phaseCT) reeval = true; else { status = 0; done = true; } }
+        else if (phaseT && n_eval_anchor >= st->tail_max_evals) { reeval = true; tail_cut = true; }   // (F^ is not worth more: ask the full objective)
         else to_head = true;
       }
       if (!phaseS) { dec_prev2 = dec_prev; dec_prev = f_old - fx; }
-    } else if (isfinite(fn) && fabs(fn - fx) <= st->ftol * fmax(fmax(fabs(fx), fabs(fn)), 1.0)) {
+    } else if (phaseT && f_valid && isfinite(fn) && fabs(fn - fx) <= st->tail_ftol * fmax(fmax(fabs(fx), fabs(fn)), 1.0)) {
+      // F^ at its noise floor (solver.h: tail_ftol) with nothing accepted since the full objective last spoke: the same
+      // search on the full objective, and no more tail
+      tail_on = 0; corr = 0; gate = MLN_GATE_F64;
+      t = 1.0; ls = 0;
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) un[e] = u[e] + d[e];
+    } else if (isfinite(fn) && fabs(fn - fx) <= (phaseT ? st->tail_ftol : st->ftol) * fmax(fmax(fabs(fx), fabs(fn)), 1.0)) {
       // The trial changed the loss by no more than the stopping tolerance but was not a sufficient decrease: the
       // search has reached the rounding noise of the objective (sums of n terms), where shrinking the step further
       // only samples that noise -- seen as 5-7 wasted passes with t = 0.2, 0.02, ... before one happened to pass.
       // This is the relative-decrease test of the accepted branch applied to the rejected trial: converged.
       // (phase C with f_valid: the accepted point IS the last fp64 evaluation -- nothing has been accepted since -- so
       //  its loss, gradient and rows' f are already fp64: no second verification of the same point)
-      if (approx && !(phaseC && f_valid)) { reeval = true; next_level = phaseS; } else { status = 0; done = true; }
+      if (approx && !(phaseCT && f_valid)) { reeval = true; next_level = phaseS; } else { status = 0; done = true; }
+    } else if (phaseT && ls >= 3) {
+      // Three rejected trials on F^: a surrogate that cannot make progress along a quasi-Newton direction has nothing more to
+      // say here (its evaluation noise, weights of thousands on a few rows, sits above the full objective's) -- ask the full
+      // objective instead of sampling that noise down to maxls: a verification pass at the accepted point -- or, if nothing
+      // was accepted since the full objective last spoke, the same search on the full objective, and no more tail
+      if (f_valid) {
+        tail_on = 0; corr = 0; gate = MLN_GATE_F64;
+        t = 1.0; ls = 0;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) un[e] = u[e] + d[e];
+      } else { reeval = true; tail_cut = true; }
     } else if (ls >= st->maxls) {
-      if (approx && !(phaseC && f_valid)) { reeval = true; next_level = phaseS; }   // the surrogate is exhausted: continue in fp64 from the accepted point
-      else { status = phaseC ? 0 : 2; done = true; }
+      if (approx && !(phaseCT && f_valid)) { reeval = true; next_level = phaseS; tail_cut = phaseT; }   // the surrogate is exhausted: continue in fp64 from the accepted point
+      else { status = phaseCT ? 0 : 2; done = true; }
     } else {
       if (isfinite(fn)) {
         const double tq = -gd * t * t / (2.0 * (fn - fx - gd * t));   // minimiser of the quadratic model
@@ -304,7 +394,8 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
     for (int e = 0; e < EPT; ++e) gm = fmax(gm, fabs(g[e]));
     gm = block_max(gm, red);
     if (!(gm > st->gtol)) {
-      if (approx) { reeval = true; next_level = phaseS; } else { status = 0; done = true; }
+      // (tail with f_valid: the accepted point IS the last full pass's -- its gradient is the one just tested)
+      if (approx && !(phaseT && f_valid)) { reeval = true; next_level = phaseS; } else { status = 0; done = true; }
     } else if (it >= st->maxiter) {
       status = 1; done = true;
     } else {
@@ -369,9 +460,11 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
       // If that is within the stopping tolerance, F itself has converged by the same measure the ftol test applies a
       // posteriori -- done, on fp64 evidence (the loss, the gradient and the rows' f of this very pass).
       if (verify && -0.5 * gd <= st->ftol * fmax(fabs(fx), 1.0)) { status = 0; done = true; }
+      // ... and if what is left to gain is below what F^ can resolve (tail_ftol), the tail has done its job: full passes finish
+      else if (new_anchor && -0.5 * gd <= st->tail_ftol * fmax(fabs(fx), 1.0)) { tail_on = 0; corr = 0; gate = MLN_GATE_F64; }
       t = t0;
       if (after_switch && st->switch_t0 > 0.0) t = st->switch_t0;
-      if (k == 0 && !resume) {
+      if (k == 0 && !resume && !tail_sync && !tail_back) {
         double g1 = 0.0;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) g1 += fabs(g[e]);
@@ -403,6 +496,17 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
 #pragma unroll
     for (int e = 0; e < EPT; ++e) un[e] = u[e];
   }
+  if (tail_req) {         // entering the importance tail: the row list's objective at the accepted point, which becomes the anchor
+    mode = MLN_SOLVE_REEVAL;
+    sub_level = MLN_TAIL_LEVEL;
+    tail_on = 1; corr = 0; n_anchor = 0; n_eval_anchor = 0;
+    tail_fa = fx; tail_over_a = over_acc;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+      un[e] = u[e];
+      if (on[e]) { b.ua[idx[e]] = u[e]; b.ga[idx[e]] = g[e]; }
+    }
+  }
   if (pause) { if (tid == 0) st->gate_after_pause = gate; gate = MLN_GATE_PAUSE; }
   if (done) gate = MLN_GATE_DONE;
 #pragma unroll
@@ -416,6 +520,9 @@ __global__ __launch_bounds__(ST) void k_solver_step(SolverBuffers b) {
     st->n_eval_sub = n_eval_sub; st->it_full = it_full; st->sub_level = sub_level;
     st->dec_prev = dec_prev; st->dec_prev2 = dec_prev2;
     st->over_acc = over_acc; st->over_cnt_acc = over_cnt_acc;
+    st->tail_on = tail_on; st->tail_sync = tail_req ? 1 : 0; st->n_eval_anchor = n_eval_anchor;
+    if (reeval && phaseT) st->tail_conv = tail_cut ? 0 : 1;
+    st->n_tail_guard = n_tail_guard; st->tail_fa = tail_fa; st->tail_over_a = tail_over_a;
     if (shrink) st->n_shrink += 1;
     if (pause) { st->rebuild_armed = (pause_reason == 1 && st->rebuild_armed > 0) ? st->rebuild_armed - 1 : 0; st->pause_reason = pause_reason; st->it_at_resume = -1; }
   }
