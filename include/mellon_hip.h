@@ -278,6 +278,37 @@ int mln_predict_gradient(mln_ctx* ctx, const mln_kernel_desc* cov, const double*
 int mln_predict_hessian(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new, int32_t d,
                         const double* centers, int64_t m, const double* W /* m */, double* out);
 
+/* ---- derivatives of block-evaluated covariance trees (more than MLN_MAX_LEAVES leaves, a deeper stack, user-defined
+ * leaves; base_cov.py:317-497, base_predictor.py:490-539).  The binding walks the tree per row block and carries every
+ * node's value and its first / second derivatives with respect to the leaves as (n x ld) device blocks (mln_ewise);
+ * these entries supply the leaf factors and contract the finished coefficient blocks.  For a stationary leaf
+ * grad_x k = g (x - c)|dims and hess_x k = g I|dims + h (x - c)(x - c)^T|dims; for Linear grad_x k = c|dims / ls.
+ *   mln_leaf_factors           K, g and (h != NULL) h of ONE built-in leaf (a one-leaf descriptor), n x ld each, columns
+ *                              m .. ld - 1 zero; the same device arithmetic as mln_kernel_matrix / mln_predict_gradient /
+ *                              mln_predict_hessian.  exact_denominator = 1: g = phi'(dist) / dist, 0 where the distance clamp
+ *                              is active (derivatives of the mean); 0: util.distance_grad's dist + 1e-12 (k_grad).  For a
+ *                              Linear leaf g = 1 / ls and h = 0.
+ *   mln_block_grad_accumulate  out[i][:] = sum_l sum_j Q_l[i][j] w_j (x_i - c_j)|dims_l  (Linear: ... w_j c_j|dims_l),
+ *                              Q_l = (dP/dk_l) g_l: one GEMM per leaf against [w C|dims_l, w].  out: n x d.
+ *   mln_block_hess_accumulate  out[i] = sum_l diag_l(sum_j w_j Qd_l[i][j]) + sum_{l <= l'} sum_j w_j Qp_ll'[i][j] S(dl dl'^T),
+ *                              dl = (sig_l x_i - c_j)|dims_l (sig = 0 for Linear), S = the product plus its transpose when
+ *                              l != l'.  Qd_l = a_l g_l (stationary leaves; NULL: none), Qp in the order (0,0) (0,1) ..
+ *                              (0,L-1) (1,1) ..: a_l h_l + a_ll gam_l^2 on the diagonal, a_ll' gam_l gam_l' off it (gam = g,
+ *                              or -1 / ls for Linear); NULL entries are identically zero.  out: n x d x d.
+ *   mln_block_kernel_grad      out[i][j][:] = sum_l A_l[i][j] (y_j - x_i)|dims_l  (Linear: A_l[i][j] x_i|dims_l): the k_grad
+ *                              of the tree with A_l = (dP/dk_l) g_l.  out: n x m x d.
+ * Coefficient blocks are DEVICE pointers with row pitch ld >= m; x, y / centers, w, out may be host or device.     */
+int mln_leaf_factors(mln_ctx* ctx, const mln_kernel_desc* leaf, const double* x, int64_t n, const double* y, int64_t m,
+                     int32_t d, int32_t exact_denominator, int64_t ld, double* K, double* g, double* h /* or NULL */);
+int mln_block_grad_accumulate(mln_ctx* ctx, const mln_leaf* leaves, int32_t n_leaves, const double* const* Q, int64_t ld,
+                              const double* x, int64_t n, int32_t d, const double* centers, int64_t m,
+                              const double* w /* m */, double* out /* n x d */);
+int mln_block_hess_accumulate(mln_ctx* ctx, const mln_leaf* leaves, int32_t n_leaves, const double* const* Qd,
+                              const double* const* Qp, int64_t ld, const double* x, int64_t n, int32_t d,
+                              const double* centers, int64_t m, const double* w /* m */, double* out /* n x d x d */);
+int mln_block_kernel_grad(mln_ctx* ctx, const mln_leaf* leaves, int32_t n_leaves, const double* const* A, int64_t ld,
+                          const double* x, int64_t n, const double* y, int64_t m, int32_t d, double* out /* n x m x d */);
+
 
 /* ---- Nystroem rank reduction (decomposition.py:23-76,126-171,213-266) ---------------------------
  * mln_eigh replaces jax.numpy.linalg.eigh at decomposition.py:50 (_eigendecomposition): A (m x m,

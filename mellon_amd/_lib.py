@@ -77,6 +77,13 @@ SYMBOLS = [
     ("mln_kernel_grad", C.c_int, [_vp, _KD, _dp, _i64, _dp, _i64, _i32, _dp]),
     ("mln_predict_gradient", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp]),
     ("mln_predict_hessian", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp]),
+    ("mln_leaf_factors", C.c_int, [_vp, _KD, _dp, _i64, _dp, _i64, _i32, _i32, _i64, _dp, _dp, _dp]),
+    ("mln_block_grad_accumulate", C.c_int, [_vp, C.POINTER(Leaf), _i32, C.POINTER(_vp), _i64, _dp, _i64, _i32, _dp, _i64,
+                                            _dp, _dp]),
+    ("mln_block_hess_accumulate", C.c_int, [_vp, C.POINTER(Leaf), _i32, C.POINTER(_vp), C.POINTER(_vp), _i64, _dp, _i64,
+                                            _i32, _dp, _i64, _dp, _dp]),
+    ("mln_block_kernel_grad", C.c_int, [_vp, C.POINTER(Leaf), _i32, C.POINTER(_vp), _i64, _dp, _i64, _dp, _i64, _i32,
+                                        _dp]),
     ("mln_kernel_gram", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp]),
     ("mln_nn_distances", C.c_int, [_vp, _dp, _i64, _dp, _i64, _i32, _i64, _dp]),
     ("mln_knn", C.c_int, [_vp, _dp, _i64, _dp, _i64, _i32, _i32, _i32, _i64, _dp, _vp]),
@@ -180,7 +187,8 @@ def _needs_program(desc, what):
     if isinstance(desc, BlockEvaluatedCov):
         raise NotImplementedError(
             f"{what} needs a covariance that lowers to one device program (built-in kernels combined with + * ** within "
-            "the program limits); user-defined Python kernels and larger trees support k(), fit and the predictive mean.")
+            "the program limits); user-defined Python kernels and larger trees support k(), k_grad, fit, the predictive mean "
+            "and its gradient / Hessian.")
 
 
 class DeviceArray:
@@ -388,10 +396,12 @@ class Context:
 
     def kernel_grad(self, desc, x, y):
         """d cov(x_i, y_j) / d y_j as an (n, m, d) array (Covariance.k_grad)."""
-        _needs_program(desc, "kernel_grad")
         x, y = _as2d(x), _as2d(y)
         if x.shape[1] != y.shape[1]:
             raise ValueError("x and y must have the same number of features")
+        if isinstance(desc, BlockEvaluatedCov):          # a tree that is not one device program
+            from . import block_derivatives
+            return block_derivatives.kernel_grad(self, desc, x, y)
         out = np.empty((x.shape[0], y.shape[0], x.shape[1]), dtype=np.float64)
         self._check(self.lib.mln_kernel_grad(self.handle, desc.ref, _ptr(x), x.shape[0], _ptr(y), y.shape[0],
                                              x.shape[1], out.ctypes.data))
@@ -399,12 +409,14 @@ class Context:
 
     def predict_gradient(self, desc, xnew, centers, W):
         """Gradient of the predictive mean with respect to each query point: (n_new, d)."""
-        _needs_program(desc, "predict_gradient")
         xnew = xnew if isinstance(xnew, DeviceArray) else _as2d(xnew)
         centers = centers if isinstance(centers, DeviceArray) else _as2d(centers)
         Wd = _f64(W)
         if Wd.ndim != 1 or Wd.shape[0] != centers.shape[0]:
             raise NotImplementedError("gradients are available for single-output predictors (weights of shape (m,))")
+        if isinstance(desc, BlockEvaluatedCov):          # a tree that is not one device program
+            from . import block_derivatives
+            return block_derivatives.predict_gradient(self, desc, xnew, centers, Wd)
         n_new, d = xnew.shape
         out = np.empty((n_new, d), dtype=np.float64)
         self._check(self.lib.mln_predict_gradient(self.handle, desc.ref, _ptr(xnew), n_new, d, _ptr(centers),
@@ -414,12 +426,14 @@ class Context:
 
     def predict_hessian(self, desc, xnew, centers, W):
         """Hessian of the predictive mean at each query point: (n_new, d, d)."""
-        _needs_program(desc, "predict_hessian")
         xnew = xnew if isinstance(xnew, DeviceArray) else _as2d(xnew)
         centers = centers if isinstance(centers, DeviceArray) else _as2d(centers)
         Wd = _f64(W)
         if Wd.ndim != 1 or Wd.shape[0] != centers.shape[0]:
             raise NotImplementedError("hessians are available for single-output predictors (weights of shape (m,))")
+        if isinstance(desc, BlockEvaluatedCov):          # a tree that is not one device program
+            from . import block_derivatives
+            return block_derivatives.predict_hessian(self, desc, xnew, centers, Wd)
         n_new, d = xnew.shape
         out = np.empty((n_new, d, d), dtype=np.float64)
         self._check(self.lib.mln_predict_hessian(self.handle, desc.ref, _ptr(xnew), n_new, d, _ptr(centers),

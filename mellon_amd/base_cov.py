@@ -131,7 +131,8 @@ class Covariance(ABC):
         if prog is not None:
             ctx = _lib.default_context()
             out = ctx.empty((x.shape[0], y.shape[0]))
-            ctx._check(ctx.lib.mln_kernel_matrix(ctx.handle, LoweredCov(*prog).ref, x.ctypes.data, x.shape[0],
+            low = LoweredCov(*prog)      # named: the descriptor points into arrays this object owns, for the whole call
+            ctx._check(ctx.lib.mln_kernel_matrix(ctx.handle, low.ref, x.ctypes.data, x.shape[0],
                                                  y.ctypes.data, y.shape[0], x.shape[1], out.ptr))
             return out
         # user-defined leaf: the subclass's k sees the columns visible here (enclosing active_dims applied, its own
@@ -155,7 +156,9 @@ class Covariance(ABC):
     def k_grad(self, x):
         """Callable y -> d k(x, y) / d y of shape (n, m, d), zeros on inactive dims (reference
         cov.py k_grad of every kernel, base_cov.py:317-497 for Add/Mul/Pow): the analytic rules are
-        evaluated by one HIP kernel over the lowered program instead of nested Python closures."""
+        evaluated by one HIP kernel over the lowered program instead of nested Python closures.  A tree that is
+        not one device program carries the same rules through its blocks (block_derivatives.py); a user-defined
+        leaf takes part when it overrides this method with the signature above, on the columns visible to it."""
         x = np.ascontiguousarray(ensure_2d(x), dtype=np.float64)
         lowered = self.lower(x.shape[1])
 

@@ -14,54 +14,13 @@
 #include <cstdlib>
 #include "mln_internal.h"
 #include "cov_program.h"
+#include "cov_leaf.h"
 
 namespace {
 
 constexpr int GR = 128;   // query rows per workgroup (predict gradient)
 constexpr int GC = 64;    // centres per LDS tile
 
-// value and radial gradient factor of one leaf.  exact_denominator = 0: distance_grad's
-// delta / (dist + 1e-12) (k_grad); 1: the exact derivative of sqrt(max(sq, 0)), delta / dist (what
-// autodiff of `_mean` gives), 0 where the clamp is active.
-__device__ __forceinline__ void leaf_value_grad(const DevLeaf& lf, double xx, double yy, double xy,
-                                                int exact_denominator, double* k, double* g) {
-  const double inv_ls = lf.alpha_inv_ls[1];
-  if (lf.kind == MLN_K_LINEAR) { *k = xy * inv_ls; *g = inv_ls; return; }
-  const double sq = xx - 2.0 * xy + yy + 1e-12;
-  const double dist = sqrt(fmax(sq, 0.0));
-  const double inv = exact_denominator ? ((sq > 0.0) ? 1.0 / dist : 0.0) : 1.0 / (dist + 1e-12);
-  switch (lf.kind) {
-    case MLN_K_MATERN32: {                                   // cov.py:84-97
-      const double f = 1.7320508075688772 * inv_ls, r = f * dist, e = exp(-r);
-      *k = (r + 1.0) * e;
-      *g = -f * r * e * inv;
-      break;
-    }
-    case MLN_K_MATERN52: {                                   // cov.py:186-199
-      const double f = 2.23606797749979 * inv_ls, r = f * dist, e = exp(-r);
-      *k = (r + r * r * 0.3333333333333333 + 1.0) * e;
-      *g = -0.3333333333333333 * e * r * (r + 1.0) * f * inv;
-      break;
-    }
-    case MLN_K_EXPQUAD: {                                    // cov.py:283-296
-      const double r = dist * inv_ls, e = exp(-0.5 * (r * r));
-      *k = e;
-      *g = -r * inv_ls * e * inv;
-      break;
-    }
-    case MLN_K_EXPONENTIAL: {                                // cov.py:380-393
-      const double r = dist * inv_ls, e = exp(-0.5 * r);
-      *k = e;
-      *g = -0.5 * inv_ls * e * inv;
-      break;
-    }
-    default: {                                               // RatQuad cov.py:481-496
-      const double r = dist * inv_ls, b = r * r / (2.0 * lf.alpha) + 1.0;
-      *k = pow(b, -lf.alpha);
-      *g = -r * inv_ls * pow(b, -lf.alpha - 1.0) * inv;
-    }
-  }
-}
 
 // out[i][j][:] = d cov(x_i, y_j) / d y_j ; one thread per pair
 __global__ void k_kernel_grad(DevCov cov, const double* __restrict__ x, int64_t n, const double* __restrict__ y,

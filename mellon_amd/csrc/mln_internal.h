@@ -23,6 +23,7 @@ __device__ __forceinline__ float mln_surrogate_bits(double v, int q32) {
 int launch_predict_mean1(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* y,
                          int64_t m, int d, const double* w, double mu, double* out);
 
+int launch_leaf_sqnorms(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, int d, double* xx);   // xx: [n_leaves][n]
 int launch_cov_diag(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, int d, double* out);
 int launch_row_sumsq(mln_ctx* ctx, const double* T, int64_t ld, int64_t rows, int64_t cols, const double* base,
                      double sign, double* out);
