@@ -1,5 +1,5 @@
-// The element epilogue of the persistent-row covariance kernels (cov_rows_impl.h, kernel_rows_prod_impl.h,
-// predict_rows.hip, predict_rows_prod.hip): distance -> stationary kernel value, as few fp64 issue slots as the
+// The element epilogue of the persistent-row covariance kernels (cov_rows_impl.h and predict_rows_impl.h over
+// rows_pipeline.h, kernel_rows_prod_impl.h): distance -> stationary kernel value, as few fp64 issue slots as the
 // arithmetic allows.  Reference: util.py:351-366 `distance` (x.x - 2 x.y + y.y + 1e-12, clamped at 0, square root),
 // cov.py:62-66 Matern32, :157-161 Matern52, :255-259 ExpQuad, :352-356 Exponential, :453-457 RatQuad.
 //

@@ -12,11 +12,9 @@
 
 #include "mln_internal.h"
 #include "rowmin_f16.h"
-#include "predict_rows_prod.h"
 #include "cov_program.h"
 #include "cov_leaf.h"
 #include "cov_rows.h"
-#include "cov_rows_q.h"
 #include "mln_options.h"
 
 namespace {
@@ -844,7 +842,7 @@ int launch_leaf_sqnorms(mln_ctx* ctx, const DevCov& cov, const double* x, int64_
   return sqnorms(ctx, cov, x, n, d, xx);
 }
 
-// The persistent-row kernels (cov_rows_impl.h, kernel_rows_prod_impl.h, predict_rows*.hip) stage centre tiles without
+// The persistent-row kernels (rows_pipeline.h: cov_rows_impl.h, predict_rows_impl.h; kernel_rows_prod_impl.h) stage centre tiles without
 // bounds checks: they are handed a COPY of the centres followed by ROWS_PAD zero rows (and norms / weights padded alike).
 constexpr int64_t ROWS_PAD = 3 * 64;   // (a predict kernel requests tile t + 2 up to t = ceil(m / 64) - 1)
 static int pad_rows(mln_ctx* ctx, const double* src, int64_t rows, int64_t cols, double* dst) {

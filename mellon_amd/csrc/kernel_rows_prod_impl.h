@@ -1,17 +1,21 @@
 // (included by kernel_rows_prod_*.hip, one translation unit per kernel kind)
 // Kernel-matrix pass of the time-sensitive fit: K = k(ls, active_dims = :-1)(x, xu) * k(ls_time, active_dims = -1)(x, xu)
 // (reference: parameters.py:641-644 builds the product, inference/conditional code consumes cov(x, xu) like any other),
-// in the persistent-row form of cov_rows_impl.h: 8 waves x 16 rows keep the MFMA A operands of their STATE columns in
-// registers and walk the centre tiles through LDS; the epilogue evaluates both leaves per element -- the state leaf from
-// the MFMA's dot product, the time leaf from the two time stamps -- and stores their product (and its 32-bit fixed-point
-// copy).  Until round 3 every 2-leaf program took the LDS-tiled VALU kernel: 33 ms of C4's 72 ms step.
+// in the persistent-row form: 8 waves x 16 rows keep the MFMA A operands of their STATE columns in registers and walk
+// the centre tiles through LDS; the epilogue evaluates both leaves per element -- the state leaf from the MFMA's dot
+// product, the time leaf from the two time stamps -- and stores their product (and its 32-bit fixed-point copy).
+//
+// This family keeps its OWN copy of the tile pipeline of rows_pipeline.h (same contracts, same structure: read the
+// reasons there).  Its 16-k-step instantiations sit at the 256-register budget and already spill; on the shared
+// pipeline the Matern52 one spilled 8 bytes more and its kernel-matrix pass measured 4.8 % slower
+// (profiles/rows_pipeline_ab.txt).  A fix to the pipeline has to be made here as well.
 #pragma once
 #include "cov_rows_impl.h"
-#include "predict_rows_prod.h"
 
 namespace {
+using covrows::NNS;
+using rowspipe::lds_barrier;
 
-// (staging, loop structure and the padded-copy contract on `y`, `yy`: cov_rows_impl.h)
 template <int KIND, bool HAS32, int KSTEPS>
 __global__ __launch_bounds__(512) void k_kernel_matrix_rows_prod(DevCov cov, const double* __restrict__ x, int64_t n,
                                                                  const double* __restrict__ y, int64_t m, int d,
@@ -192,8 +196,11 @@ static int launch_rows_prod_kind(mln_ctx* ctx, const DevCov& cov, const double* 
   return MLN_OK;
 }
 
-#define MLN_DEFINE_ROWS_PROD_KIND(NAME, KIND)                                                                            \
-  int NAME(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* y, int64_t m, int d,               \
-           const double* xx, const double* yy, double* out, int64_t ldo, double add_diag, float* out32, int q32) {       \
+// launch_kernel_matrix_rows_kind<KIND, true> (cov_rows.h) is this family's launcher
+#define MLN_DEFINE_ROWS_PROD_KIND(KIND)                                                                                  \
+  template <>                                                                                                            \
+  int launch_kernel_matrix_rows_kind<KIND, true>(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n,            \
+                                                 const double* y, int64_t m, int d, const double* xx, const double* yy,  \
+                                                 double* out, int64_t ldo, double add_diag, float* out32, int q32) {     \
     return launch_rows_prod_kind<KIND>(ctx, cov, x, n, y, m, d, xx, yy, out, ldo, add_diag, out32, q32);                 \
   }

@@ -1,4 +1,4 @@
-// k_predict_mean_rows_prod for MLN_K_EXPONENTIAL (see predict_rows_prod_impl.h)
-#include "predict_rows_prod_impl.h"
+// k_predict_mean_rows_prod for MLN_K_EXPONENTIAL (see predict_rows_impl.h)
+#include "predict_rows_impl.h"
 
-MLN_DEFINE_PREDICT_ROWS_PROD_KIND(launch_predict_mean_rows_prod_exponential, MLN_K_EXPONENTIAL)
+MLN_INSTANTIATE_PREDICT_MEAN_ROWS(MLN_K_EXPONENTIAL, true)

@@ -661,6 +661,36 @@ def test_kernel_matrix_persistent_rows(ctx, name, d):
     assert (np.abs(K - ref)[big] / ref[big]).max() < 1e-11       # (summation order of the d-term dot products differs)
 
 
+def test_kernel_matrix_persistent_rows_diagonal_term(ctx):
+    """The persistent-row kernel with a diagonal term: a fit prepared with 4096 landmarks in d = 8 builds
+    cov(xu, xu) + jitter I on it (n = m = 4096; a diagonal term sends every tile through the clamped loop), read back
+    through the landmark factor: Lp Lp^T == the oracle's K + jitter I to the tolerances of
+    test_kernel_matrix_persistent_rows for non-coincident pairs (1e-12 absolute, 1e-11 relative above 1e-3).  The
+    diagonal pairs ARE coincident, but Matern52 is smooth at 0 (k = 1 - 5 r^2 / 6 + ...): the ~1e-14 rounding noise of
+    xx - 2xy + yy moves it by less than 1e-13.  The factorisation's own rounding rides on top: at most
+    (m + 1) 2^-53 sqrt(a_ii a_jj) = 4.6e-13 per entry (Higham, Accuracy and Stability, thm 10.3), in practice
+    ~sqrt(m) 2^-53.  At ls = 1.7, jitter = 1e-3 the oracle's matrix factors in NumPy (eigenvalues 0.047 .. 174; checked
+    on the CPU)."""
+    from mellon_amd import cov
+    m, d, jitter = 4096, 8, 1e-3
+    rng = np.random.default_rng(4096)
+    xu = rng.normal(size=(m, d)) * 1.5
+    x = rng.normal(size=(200, d)) * 1.5
+    c = cov.Matern52(1.7)
+    fit = ctx.fit_prepare(c.lower(d), x, xu, jitter)
+    Lp = fit.Lp()
+    assert Lp.shape == (m, m) and np.all(np.isfinite(Lp))
+    Lp = np.tril(Lp)
+    ref = _pair(c)(xu, xu) + jitter * np.eye(m)
+    err = np.abs(Lp @ Lp.T - ref)
+    print(f"max |Lp Lp^T - (K + jitter I)| = {err.max():.3e}, on the diagonal {np.diag(err).max():.3e}")
+    big = ref > 1e-3
+    print(f"max relative error on the {big.sum()} entries above 1e-3: {(err[big] / ref[big]).max():.3e}")
+    assert err.max() < 1e-12
+    assert big.sum() > 10000
+    assert (err[big] / ref[big]).max() < 1e-11
+
+
 def _digit_gram_exact(a):
     """What csrc/gram_i8.hip computes, in exact int64 arithmetic: three balanced base-256 digits of
     q = round(a * 8355711) and all nine digit-pair products -- i.e. q^T q."""
