@@ -273,6 +273,15 @@ int mln_kernel_grad(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, i
 int mln_predict_gradient(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new,
                          int32_t d, const double* centers, int64_t m, const double* W /* m */,
                          double* out /* n_new x d */);
+/* The same for a predictor with p outputs (FunctionEstimator on p columns; the time grid of PredictorTime with the time
+ * factor folded into the weights): out[i][q][:] = sum_j W[j][q] d cov(x_i, c_j) / d x_i.  p == 1 is mln_predict_gradient
+ * bit for bit.  Stationary leaves and n_new m >= 2^16: the coefficient matrices (dP/dk_l) g_l are written once per row
+ * chunk WITHOUT weights, and blocks of outputs are contracted by one GEMM per leaf against [W_q C|dims_l, W_q] -- the
+ * covariance epilogue runs once per (row, centre) pair, whatever p is.  Otherwise (a Linear leaf, fewer pairs) column by
+ * column through the single-output routes, with their bits.                                                          */
+int mln_predict_gradient_multi(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new, int32_t d,
+                               const double* centers, int64_t m, const double* W /* m x p, row-major */, int64_t p,
+                               double* out /* n_new x p x d */);
 /* Hessian of the mean at every row of xnew, out: n_new x d x d (base_predictor.py:507-521: jacfwd(jacrev(_mean));
  * here the closed-form second derivatives of the kernels, contracted with the weights on the matrix cores).      */
 int mln_predict_hessian(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new, int32_t d,

@@ -76,6 +76,7 @@ SYMBOLS = [
     ("mln_kernel_matrix", C.c_int, [_vp, _KD, _dp, _i64, _dp, _i64, _i32, _dp]),
     ("mln_kernel_grad", C.c_int, [_vp, _KD, _dp, _i64, _dp, _i64, _i32, _dp]),
     ("mln_predict_gradient", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp]),
+    ("mln_predict_gradient_multi", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dp]),
     ("mln_predict_hessian", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp]),
     ("mln_leaf_factors", C.c_int, [_vp, _KD, _dp, _i64, _dp, _i64, _i32, _i32, _i64, _dp, _dp, _dp]),
     ("mln_block_grad_accumulate", C.c_int, [_vp, C.POINTER(Leaf), _i32, C.POINTER(_vp), _i64, _dp, _i64, _i32, _dp, _i64,
@@ -408,21 +409,41 @@ class Context:
         return out
 
     def predict_gradient(self, desc, xnew, centers, W):
-        """Gradient of the predictive mean with respect to each query point: (n_new, d)."""
+        """Gradient of the predictive mean with respect to each query point: (n_new, d) for weights of shape (m,),
+        (n_new, p, d) for (m, p) -- every output in one device call (mln_predict_gradient_multi)."""
         xnew = xnew if isinstance(xnew, DeviceArray) else _as2d(xnew)
         centers = centers if isinstance(centers, DeviceArray) else _as2d(centers)
         Wd = _f64(W)
-        if Wd.ndim != 1 or Wd.shape[0] != centers.shape[0]:
-            raise NotImplementedError("gradients are available for single-output predictors (weights of shape (m,))")
+        if Wd.ndim not in (1, 2) or Wd.shape[0] != centers.shape[0]:
+            raise ValueError(f"weights of shape {Wd.shape} do not go with {centers.shape[0]} centres: (m,) or (m, p)")
         if isinstance(desc, BlockEvaluatedCov):          # a tree that is not one device program
             from . import block_derivatives
+            if Wd.ndim == 2:
+                return np.stack([block_derivatives.predict_gradient(self, desc, xnew, centers, np.ascontiguousarray(Wd[:, q]))
+                                 for q in range(Wd.shape[1])], axis=1)
             return block_derivatives.predict_gradient(self, desc, xnew, centers, Wd)
         n_new, d = xnew.shape
+        if Wd.ndim == 2:
+            p = Wd.shape[1]
+            out = np.empty((n_new, p, d), dtype=np.float64)
+            if p:
+                self._check(self.lib.mln_predict_gradient_multi(self.handle, desc.ref, _ptr(xnew), n_new, d, _ptr(centers),
+                                                                centers.shape[0], Wd.ctypes.data, p, out.ctypes.data))
+            return out
         out = np.empty((n_new, d), dtype=np.float64)
         self._check(self.lib.mln_predict_gradient(self.handle, desc.ref, _ptr(xnew), n_new, d, _ptr(centers),
                                                   centers.shape[0], Wd.ctypes.data, out.ctypes.data))
         return out
 
+    def leaf_factors(self, leaf_desc, x, y, exact_denominator=True):
+        """(K, g), (n, m) each, of ONE built-in leaf (a one-leaf descriptor): its values and the radial factor of its
+        gradient, grad_x k(x_i, y_j) = g_ij (x_i - y_j)|dims (mln_leaf_factors)."""
+        x, y = _as2d(x), _as2d(y)
+        (n, d), m = x.shape, y.shape[0]
+        K, g = np.zeros((n, m), dtype=np.float64), np.zeros((n, m), dtype=np.float64)
+        self._check(self.lib.mln_leaf_factors(self.handle, leaf_desc.ref, x.ctypes.data, n, y.ctypes.data, m, d,
+                                              int(bool(exact_denominator)), m, K.ctypes.data, g.ctypes.data, None))
+        return K, g
 
     def predict_hessian(self, desc, xnew, centers, W):
         """Hessian of the predictive mean at each query point: (n_new, d, d)."""

@@ -334,3 +334,34 @@ class Pow(CovariancePair):
 
     def __repr__(self):
         return "(" + repr(self.left) + " ** " + repr(self.right) + ")"
+
+
+_STATIONARY_KINDS = (_lib.K_MATERN32, _lib.K_MATERN52, _lib.K_EXPQUAD, _lib.K_EXPONENTIAL, _lib.K_RATQUAD)
+
+
+def split_state_time(cov_func, d):
+    """The two factors of a separable time-sensitive covariance over d columns (the last one is time), or None.
+
+    `(state, time)`: `state` is the LoweredCov of the state factor over all d columns (no leaf reads column d - 1), `time`
+    the one-leaf LoweredCov of the time factor for 1-column arrays (its dim remapped to 0).  The tree qualifies when it
+    is a top-level `Mul` of two covariances, in either order, one a single built-in stationary leaf whose composed active
+    dims are exactly [d - 1], the other a sub-tree that is one device program and stays off column d - 1 -- what
+    `parameters.compute_cov_func` builds.  active_dims compose as in `_emit`, the `Mul` node's own included.  Anything
+    else (Add / Pow at the top, a scalar factor, a Linear or user-defined time leaf, a state side that only a BlockCov
+    evaluates) gives None."""
+    d = int(d)
+    if type(cov_func) is not Mul or not callable(cov_func.right) or d < 2:
+        return None
+    cols = compose_active_dims(np.arange(d), cov_func.active_dims)
+    for time, state in ((cov_func.right, cov_func.left), (cov_func.left, cov_func.right)):
+        if isinstance(time, CovariancePair) or time._user_defined() or time._kind not in _STATIONARY_KINDS:
+            continue
+        tdims = compose_active_dims(cols, time.active_dims)
+        if tdims.shape != (1,) or int(tdims[0]) != d - 1:
+            continue
+        prog = state._try_program(cols)
+        if prog is None or any((d - 1) in np.asarray(leaf[3]) for leaf in prog[0]):
+            continue
+        leaf = (time._kind, getattr(time, "ls", 1.0), getattr(time, "alpha", 1.0), np.zeros(1, dtype=np.int32))
+        return LoweredCov(*prog), LoweredCov([leaf], [(_lib.OP_LEAF, 0, 0.0)])
+    return None

@@ -86,9 +86,7 @@ class Predictor:
         contracted with the weights on the device.  `jit` is accepted and ignored."""
         x = self._check_features(x)
         ctx, desc = _lib.default_context(), self.cov_func.lower(self.n_input_features)
-        if self.weights.ndim == 2:      # p outputs: (n, p, d), the layout derivatives.gradient gives (derivatives.py:76-80)
-            return np.stack([ctx.predict_gradient(desc, x, self.centers, np.ascontiguousarray(self.weights[:, c]))
-                             for c in range(self.weights.shape[1])], axis=1)
+        # p outputs: (n, p, d), the layout derivatives.gradient gives (derivatives.py:76-80), in one device call
         return ctx.predict_gradient(desc, x, self.centers, self.weights)
 
     # -- predictive uncertainty (base_predictor.py:330-428; conditional.py _covariance / _mean_covariance) --
@@ -288,12 +286,12 @@ class ExpPredictor(Predictor):
     __call__ = mean
 
     def gradient(self, x, jit=True):
-        return np.exp(Predictor.mean(self, x))[:, None] * Predictor.gradient(self, x)
+        return np.exp(Predictor.mean(self, x))[..., None] * Predictor.gradient(self, x)
 
     def hessian(self, x, jit=True):
         """Hessian of exp(f): e^f (H_f + grad f grad f^T)."""
         g = Predictor.gradient(self, x)
-        return np.exp(Predictor.mean(self, x))[:, None, None] * (Predictor.hessian(self, x) + g[:, :, None] * g[:, None, :])
+        return np.exp(Predictor.mean(self, x))[..., None, None] * (Predictor.hessian(self, x) + g[..., :, None] * g[..., None, :])
 
 
 class PredictorTime(Predictor):
@@ -313,23 +311,75 @@ class PredictorTime(Predictor):
     @make_multi_time_argument
     def gradient(self, x, time=None, jit=True):
         """Gradient with respect to the state columns at the given time(s) (base_predictor.py:1094-1124)."""
-        return Predictor.gradient(self, self._with_time(x, time))[:, :-1]
+        return Predictor.gradient(self, self._with_time(x, time))[..., :-1]
 
     @make_multi_time_argument
     def hessian(self, x, time=None, jit=True):
         """Hessian with respect to the state columns at the given time(s) (base_predictor.py:1127-1159)."""
-        return Predictor.hessian(self, self._with_time(x, time))[:, :-1, :-1]
+        return Predictor.hessian(self, self._with_time(x, time))[..., :-1, :-1]
 
     @make_multi_time_argument
     def hessian_log_determinant(self, x, time=None, jit=True):
         """base_predictor.py:1162-1194."""
-        sign, logdet = np.linalg.slogdet(Predictor.hessian(self, self._with_time(x, time))[:, :-1, :-1])
+        sign, logdet = np.linalg.slogdet(Predictor.hessian(self, self._with_time(x, time))[..., :-1, :-1])
         return sign, logdet
 
     @make_multi_time_argument
     def time_derivative(self, x, time=None, jit=True):
         """Derivative with respect to time (base_predictor.py:1052-1091)."""
-        return Predictor.gradient(self, self._with_time(x, time))[:, -1]
+        return Predictor.gradient(self, self._with_time(x, time))[..., -1]
+
+    # -- multi_time on a grid: all T times in one pass (util.make_multi_time_argument looks for `_grid_<method>`) ----------
+    # For cov = k_state(x, c) k_time(t, s) (parameters.compute_cov_func) the state factor carries all of the n m d work and
+    # is the same for every time; the time factor folds into the weights:
+    #   mean[i, t]  = mu + sum_j k_state(x_i, c_j) E[j, t],   E[j, t] = w_j k_time(t, s_j)
+    #   d/dt [i, t] =      sum_j k_state(x_i, c_j) D[j, t],   D[j, t] = w_j g(t, s_j) (t - s_j)
+    #   grad_x[i, t] = the T-output gradient of the state kernel with weights E
+    # -- one multi-output prediction of the state kernel (kernel-matrix chunks + a GEMM) instead of T fused predictions.
+    _GRID_MIN_WORK = 1 << 16      # n_new m T below which the per-time loop runs: launch-bound either way
+
+    def _grid_setup(self, Xnew, times, want_derivative=False):
+        """(state descriptor, [Xnew | 0], E, D or None), or None when the per-time loop has to run."""
+        from .base_cov import split_state_time
+        if isinstance(Xnew, _lib.DeviceArray) or self.weights.ndim != 1 or times.shape[0] < 2:
+            return None
+        split = split_state_time(self.cov_func, self.n_input_features)
+        if split is None:
+            return None
+        Xq = self._with_time(Xnew, 0.0)            # the loop's own validation; the state factor never reads the time column
+        if Xq.shape[0] * self.centers.shape[0] * times.shape[0] < self._GRID_MIN_WORK:
+            return None
+        state, time_leaf = split
+        s = np.ascontiguousarray(self.centers[:, -1:])
+        K, g = _lib.default_context().leaf_factors(time_leaf, times.reshape(-1, 1), s)        # (T, m) each
+        E = np.ascontiguousarray((K * self.weights).T)
+        D = np.ascontiguousarray((g * (times[:, None] - s[:, 0]) * self.weights).T) if want_derivative else None
+        return state, Xq, E, D
+
+    def _grid_mean(self, Xnew, time=None, normalize=False, times=None):
+        normalize = validate_bool(normalize, "normalize")
+        if normalize and (self.n_obs is None or self.n_obs == 0):
+            return NotImplemented                  # the loop raises the predictor's own error
+        setup = self._grid_setup(validate_array(Xnew, "Xnew"), times)
+        if setup is None:
+            return NotImplemented
+        state, Xq, E, _ = setup
+        out = _lib.default_context().predict_mean(state, Xq, self.centers, E, self.mu)
+        return out - log(self.n_obs) if normalize else out
+
+    def _grid_gradient(self, x, time=None, jit=True, times=None):
+        setup = self._grid_setup(x, times)
+        if setup is None:
+            return NotImplemented
+        state, Xq, E, _ = setup
+        return np.ascontiguousarray(_lib.default_context().predict_gradient(state, Xq, self.centers, E)[..., :-1])
+
+    def _grid_time_derivative(self, x, time=None, jit=True, times=None):
+        setup = self._grid_setup(x, times, want_derivative=True)
+        if setup is None:
+            return NotImplemented
+        state, Xq, _, D = setup
+        return _lib.default_context().predict_mean(state, Xq, self.centers, D, 0.0)
 
     def _with_time(self, Xnew, time):
         Xnew = np.ascontiguousarray(ensure_2d(validate_array(Xnew, "Xnew")), dtype=np.float64)

@@ -181,7 +181,8 @@ __global__ __launch_bounds__(256) void k_kernel_matrix_mfma(DevCov cov, const do
 }
 
 // ---- predictor gradient, single stationary leaf: grad_i = sum_j w_j g_ij (x_i - c_j)|dims -------------------
-//   Q (rows x m) = w_j g_ij                     one covariance-tile pass (this kernel)
+//   Q (rows x m) = w_j g_ij                     one covariance-tile pass (this kernel; w == nullptr: Q = g_ij, the
+//                                               weight-less form of the p-output route below)
 //   T = Q [C|dims , 1]                          one GEMM on the matrix cores
 //   grad_i[dims] = x_i[dims] T_i,last - T_i,k   (k_grad_combine)
 __global__ __launch_bounds__(256) void k_grad_coeff(DevCov cov, const double* __restrict__ x, int64_t n,
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(256) void k_grad_coeff(DevCov cov, const double* __
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t c = col0 + tx * 4 + j;
-      if (c < ldo) out[r * ldo + c] = (c < m) ? val[i][j] * w[c] : 0.0;
+      if (c < ldo) out[r * ldo + c] = (c < m) ? (w ? val[i][j] * w[c] : val[i][j]) : 0.0;   // w == nullptr: Q = g
     }
   }
 }
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(256) void k_grad_coeff_multi(DevCov cov, const doub
         gf[l] = leaf_grad_coeff(cov.leaves[l], xr[l][i], yr[l][j], acc[l][i][j]);
       }
       program_adjoints(cov, kv, a);
-      const double wc = (c < m) ? w[c] : 0.0;
+      const double wc = (c < m) ? (w ? w[c] : 1.0) : 0.0;   // w == nullptr: Q_l = (dP/dk_l) g_l (1.0 * v is v exactly)
 #pragma unroll
       for (int l = 0; l < MLN_MAX_LEAVES; ++l)
         if (l < cov.n_leaves) out[(int64_t)l * leaf_stride + r * ldo + c] = wc * a[l] * gf[l];
@@ -314,6 +315,41 @@ __global__ void k_grad_combine_leaf(DevCov cov, int leaf, const double* __restri
   const int k = (int)(idx % lf.ndims);
   const int dim = cov.dims[lf.dims_off + k];
   out[i * d + dim] += x[i * d + dim] * T[i * ldt + lf.ndims] - T[i * ldt + k];
+}
+
+// ---- predictor gradient for p outputs (launch_predict_gradient_batched): the coefficient matrices above are written
+// WITHOUT weights (w == nullptr), the weights move into the centre operand of the GEMM, pb outputs side by side:
+//   Z_l[j][q (nd_l + 1) + k] = W[j][q0 + q] c_j[dims_l[k]] (k < nd_l),  W[j][q0 + q] (k == nd_l),  zero up to ldz
+__global__ void k_grad_weighted_centres(DevCov cov, int leaf, const double* __restrict__ c, int64_t m, int d,
+                                        const double* __restrict__ W, int64_t p, int64_t q0, int64_t pb,
+                                        double* __restrict__ Z, int64_t ldz) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= m * ldz) return;
+  const DevLeaf lf = cov.leaves[leaf];
+  const int64_t j = idx / ldz, col = idx % ldz, nd1 = lf.ndims + 1;
+  const int64_t q = col / nd1;
+  const int k = (int)(col % nd1);
+  double v = 0.0;
+  if (q < pb) {
+    v = W[j * p + q0 + q];
+    if (k < lf.ndims) v *= c[j * d + cov.dims[lf.dims_off + k]];
+  }
+  Z[idx] = v;
+}
+
+// out[i][q0 + q][dims_l[k]] += x_i[dims_l[k]] T_i,q(nd+1)+nd - T_i,q(nd+1)+k   (one thread per (i, q, k); out is rows x p x d,
+// zeroed by the launcher; leaves and output blocks run one after the other on the stream)
+__global__ void k_grad_combine_outputs(DevCov cov, int leaf, const double* __restrict__ T, int64_t ldt,
+                                       const double* __restrict__ x, int64_t rows, int d, int64_t p, int64_t q0,
+                                       int64_t pb, double* __restrict__ out) {
+  const DevLeaf lf = cov.leaves[leaf];
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * pb * lf.ndims) return;
+  const int k = (int)(idx % lf.ndims);
+  const int64_t q = (idx / lf.ndims) % pb, i = idx / (lf.ndims * pb);
+  const int dim = cov.dims[lf.dims_off + k];
+  const double* __restrict__ Ti = T + i * ldt + q * (lf.ndims + 1);
+  out[(i * p + q0 + q) * d + dim] += x[i * d + dim] * Ti[lf.ndims] - Ti[k];
 }
 
 // ---- predictor Hessian (base_predictor.py:507-521: jacfwd(jacrev(mean))) --------------------------------------
@@ -1149,5 +1185,81 @@ int launch_predict_gradient_gemm(mln_ctx* ctx, const DevCov& cov, const double* 
   hipError_t e = hipGetLastError();
   (void)hipStreamSynchronize(ctx->stream);
   if (rc == MLN_OK && e != hipSuccess) rc = mln_hip_fail(ctx, e, "predict_gradient_gemm", __FILE__, __LINE__);
+  return rc;
+}
+
+// Predictor gradient of p outputs at once, stationary leaves only (single leaf or composite program): out is n x p x d.
+//   per row chunk:  Q_l = (dP/dk_l) g_l  (rows x m, no weights)              ONE covariance-tile pass, whatever p is
+//   per output block [q0, q0 + pb) and leaf:  T = Q_l Z_l                     one GEMM, pb (nd_l + 1) columns
+//                                             out[:, q0 + q, dims_l] += x T_nd - T_k
+// pb (nd_max + 1) <= GRAD_MULTI_COLS columns per GEMM (MELLON_AMD_GRAD_COLS overrides it, read at every call); rows per
+// chunk: at most 32768, and Q (L ldq per row) plus T (ldz per row) within GRAD_MULTI_SCRATCH doubles (never below 64 rows).
+constexpr int64_t GRAD_MULTI_COLS = 512;
+constexpr int64_t GRAD_MULTI_SCRATCH = (int64_t)1 << 27;   // 1 GiB of doubles for Q and T together
+
+int launch_predict_gradient_batched(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c,
+                                    int64_t m, int d, const double* W, int64_t p, double* out) {
+  if (n == 0 || p == 0) return MLN_OK;
+  const int L = cov.n_leaves;
+  int nd_max = 0;
+  for (int l = 0; l < L; ++l) nd_max = cov.leaves[l].ndims > nd_max ? cov.leaves[l].ndims : nd_max;
+  int64_t cols = GRAD_MULTI_COLS;
+  if (const char* e = std::getenv("MELLON_AMD_GRAD_COLS")) {
+    const long long v = std::atoll(e);
+    if (v >= 1 && v <= 4096) cols = v;
+  }
+  int64_t pb_max = cols / (nd_max + 1);
+  if (pb_max < 1) pb_max = 1;
+  if (pb_max > p) pb_max = p;
+  const int64_t ldq = ((m + 15) / 16) * 16, ldz = ((pb_max * (nd_max + 1) + 15) / 16) * 16;
+  int64_t chunk = GRAD_MULTI_SCRATCH / ((int64_t)L * ldq + ldz);
+  chunk = (chunk / 64) * 64;
+  if (chunk > 32768) chunk = 32768;
+  if (chunk < 64) chunk = 64;
+  if (chunk > n) chunk = n;
+  const bool single = cov.n_toks == 1;          // one bare leaf: k_grad_coeff, else one matrix per leaf
+  double* norms = nullptr;
+  DevBuf<double> Q, T, Z;
+  MLN_TRY(mln_scratch(ctx, sizeof(double) * (size_t)L * (size_t)(n + m), (void**)&norms));
+  double* xx = norms;                        // [L][n]
+  double* yy = norms + (size_t)L * n;        // [L][m]
+  MLN_TRY(sqnorms(ctx, cov, x, n, d, xx));
+  MLN_TRY(sqnorms(ctx, cov, c, m, d, yy));
+  const int64_t leaf_stride = chunk * ldq;
+  MLN_TRY(Q.alloc(ctx, (size_t)L * leaf_stride, "Q"));
+  MLN_TRY(T.alloc(ctx, (size_t)chunk * ldz, "T"));
+  MLN_TRY(Z.alloc(ctx, (size_t)m * ldz, "Z"));
+  MLN_HIP(ctx, hipMemsetAsync(out, 0, sizeof(double) * (size_t)n * (size_t)p * d, ctx->stream));
+  int rc = MLN_OK;
+  const int64_t tiles_n = (ldq + TN - 1) / TN;
+  for (int64_t r0 = 0; r0 < n && rc == MLN_OK; r0 += chunk) {
+    const int64_t rows = (n - r0 < chunk) ? (n - r0) : chunk;
+    const int64_t nblk = tiles_n * ((rows + TM - 1) / TM);
+    if (single)
+      hipLaunchKernelGGL(k_grad_coeff, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, cov, x + r0 * d, rows, c, m, d,
+                         xx + r0, yy, (const double*)nullptr, Q.get(), ldq, tiles_n);
+    else
+      hipLaunchKernelGGL(k_grad_coeff_multi, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, cov, x + r0 * d, rows, c, m,
+                         d, xx + r0, n, yy, (const double*)nullptr, Q.get(), ldq, leaf_stride, tiles_n);
+    for (int64_t q0 = 0; q0 < p && rc == MLN_OK; q0 += pb_max) {
+      const int64_t pb = (p - q0 < pb_max) ? (p - q0) : pb_max;
+      for (int l = 0; l < L && rc == MLN_OK; ++l) {
+        const int nd = cov.leaves[l].ndims;
+        if (nd == 0) continue;
+        hipLaunchKernelGGL(k_grad_weighted_centres, dim3((unsigned)((m * ldz + 255) / 256)), dim3(256), 0, ctx->stream, cov,
+                           l, c, m, d, W, p, q0, pb, Z.get(), ldz);
+        GemmArgs g{};
+        g.A = Q + (size_t)l * leaf_stride; g.lda = ldq; g.ta = 0; g.B = Z; g.ldb = ldz; g.tb = 0;
+        g.C = T; g.ldc = ldz; g.M = rows; g.N = pb * (nd + 1); g.K = m; g.alpha = 1.0; g.beta = 0.0; g.split_k = 1;
+        rc = launch_dgemm(ctx, g);
+        if (rc != MLN_OK) break;
+        hipLaunchKernelGGL(k_grad_combine_outputs, dim3((unsigned)((rows * pb * nd + 255) / 256)), dim3(256), 0,
+                           ctx->stream, cov, l, T.get(), ldz, x + r0 * d, rows, d, p, q0, pb, out + r0 * p * d);
+      }
+    }
+  }
+  hipError_t e = hipGetLastError();
+  (void)hipStreamSynchronize(ctx->stream);
+  if (rc == MLN_OK && e != hipSuccess) rc = mln_hip_fail(ctx, e, "predict_gradient_batched", __FILE__, __LINE__);
   return rc;
 }

@@ -87,6 +87,12 @@ int launch_predict_hessian(mln_ctx* ctx, const DevCov& cov, const double* x, int
                            int d, const double* w, double* out);              // out: n x d x d
 int launch_predict_gradient(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
                             int d, const double* w, double* out);
+// p outputs, W m x p row-major, out n x p x d.  _batched (cov_kernels.hip): stationary leaves, one weight-less coefficient
+// pass per row chunk and GEMMs over blocks of outputs; _multi (cov_grad.hip) picks it, or launch_predict_gradient per column
+int launch_predict_gradient_batched(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c,
+                                    int64_t m, int d, const double* W, int64_t p, double* out);
+int launch_predict_gradient_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
+                                  int d, const double* W, int64_t p, double* out);
 
 // eigh.hip: symmetric eigensolver (block one-sided Jacobi); w_host ascending, Vrows row j = eigenvector j
 int dev_eigh(mln_ctx* ctx, const double* A, int64_t m, int64_t lda, double* w_host, double* Vrows, int64_t ldv,

@@ -242,7 +242,9 @@ test_rank.__test__ = False       # a utility of the reference's API, not a pytes
 def make_multi_time_argument(func):
     """Decorator adding an optional `multi_time` argument to a method that takes `time` (util.py:206-265): the method
     runs once per value and the results are stacked along axis 1 (element-wise for tuple results), the layout of the
-    reference's `vmap(..., out_axes=1)`."""
+    reference's `vmap(..., out_axes=1)`.  An object that can evaluate all times in one pass offers `_grid_<method name>`: it
+    gets the call's own arguments and the 1-D `times`, and returns the stacked result or `NotImplemented` (then the loop
+    runs)."""
     sig = inspect.signature(func)
     new_sig = sig.replace(parameters=list(sig.parameters.values()) + [
         inspect.Parameter("multi_time", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=None)])
@@ -255,6 +257,11 @@ def make_multi_time_argument(func):
         if kwargs.get("time", None) is not None:
             raise ValueError("Cannot specify both 'time' and 'multi_time' arguments")
         times = np.asarray(multi_time, dtype=np.float64).reshape(-1)
+        grid = getattr(self, "_grid_" + func.__name__, None)      # all times in one pass, where the object has one
+        if grid is not None:
+            out = grid(*args, **kwargs, times=times)
+            if out is not NotImplemented:
+                return out
         outs = [func(self, *args, **kwargs, time=float(t)) for t in times]
         if isinstance(outs[0], tuple):
             return tuple(np.stack([o[k] for o in outs], axis=1) for k in range(len(outs[0])))
