@@ -499,6 +499,27 @@ int mln_diag_dgemm(mln_ctx* ctx, int32_t ta, int32_t tb, int64_t M, int64_t N, i
  * out[1] = largest absolute value.  any_size != 0: the mixed kernel also below the size where the policy selects it. */
 int mln_diag_dgemm_compare(mln_ctx* ctx, int32_t ta, int32_t tb, int64_t M, int64_t N, int64_t K, int32_t lower_only,
                            int32_t kmode, double beta, int32_t any_size, double* out);
+/* One launch of the internal GEMM on caller-supplied host buffers, for tests that hold an exact expected result
+ * (tests/gemm_reference.py).  The fields are those of the internal GEMM; in addition
+ *   a_off, b_off, c_off  element offsets of the operands in their buffers (odd: 8- but not 16-byte aligned: scalar loads)
+ *   bsa, bsb, bsc        batch > 1: distance in elements between consecutive operands (bsc >= split_k * M * ldc)
+ *   mix                  0: the single-size tile kernels only; otherwise the launch policy's own choice
+ *   sum_partials         split_k > 1 only: follow with the fixed-order sum of the partials, out = beta * out + sum
+ *   c_in_a_col           >= 0: C lies INSIDE the A operand, at this element offset from its start, with ldc = lda
+ *   c_in_b_off           >= 0: the same inside the B operand, ldc = ldb   (both -1: C is the third buffer)
+ * split_k > 1: C holds split_k partial results M * ldc elements apart (alpha applied, beta not).  C is uploaded, and
+ * downloaded whole; in place its count must equal that of the aliased buffer, whose final contents it receives.
+ * MLN_ERR_ARG unless whole rows of every operand lie inside the given element counts. */
+typedef struct mln_gemm_spec {
+  int32_t ta, tb, lower_only, kmode, split_k, batch, mix, sum_partials;
+  int64_t M, N, K, lda, ldb, ldc;
+  int64_t a_off, b_off, c_off;
+  int64_t bsa, bsb, bsc;
+  int64_t c_in_a_col, c_in_b_off;
+  double alpha, beta;
+} mln_gemm_spec;
+int mln_diag_dgemm_run(mln_ctx* ctx, const mln_gemm_spec* spec, const double* A, int64_t a_count, const double* B,
+                       int64_t b_count, double* C, int64_t c_count, double* out /* M * ldc, or NULL */, int64_t out_count);
 /* The integer Gram of the preconditioner in isolation (csrc/gram_i8.hip): out (m x m) = Q^T Q / 8355711^2 with
  * Q = round(A * 8355711), A rows x m with values in [0, 1] (host or device); terms below 2^-23 relative are dropped.
  * ms_out (may be NULL): milliseconds per call over `reps` calls.  Not a reference operation: the reference forms the

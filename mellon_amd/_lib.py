@@ -42,6 +42,14 @@ class SolverOpts(C.Structure):
                 ("gtol", C.c_double)]
 
 
+class GemmSpec(C.Structure):
+    """mln_gemm_spec: one launch of the internal GEMM (mln_diag_dgemm_run)."""
+    _fields_ = ([(n, C.c_int32) for n in ("ta", "tb", "lower_only", "kmode", "split_k", "batch", "mix", "sum_partials")] +
+                [(n, C.c_int64) for n in ("M", "N", "K", "lda", "ldb", "ldc", "a_off", "b_off", "c_off", "bsa", "bsb", "bsc",
+                                          "c_in_a_col", "c_in_b_off")] +
+                [("alpha", C.c_double), ("beta", C.c_double)])
+
+
 class KernelDesc(C.Structure):
     _fields_ = [("n_leaves", C.c_int32), ("n_toks", C.c_int32), ("leaves", C.POINTER(Leaf)),
                 ("toks", C.POINTER(Tok))]
@@ -141,6 +149,7 @@ SYMBOLS = [
     ("mln_diag_gram_i8", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, C.POINTER(_dbl)]),
     ("mln_diag_dgemm", C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _i32, C.POINTER(_dbl)]),
     ("mln_diag_dgemm_compare", C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _dbl, _i32, C.POINTER(_dbl)]),
+    ("mln_diag_dgemm_run", C.c_int, [_vp, C.POINTER(GemmSpec), _dp, _i64, _dp, _i64, _dp, _i64, _dp, _i64]),
 ]
 
 _lib = None
@@ -815,6 +824,21 @@ class Context:
         r = (C.c_double * 2)()
         self._check(self.lib.mln_diag_dgemm_compare(self.handle, int(ta), int(tb), M, N, K, lower_only, kmode, float(beta), 2, r))
         return float(r[0])
+
+    def diag_dgemm_run(self, spec, A, B, C0, out0=None):
+        """One launch of the internal GEMM on flat host buffers (mln_diag_dgemm_run).  spec: a mapping with the fields of
+        GemmSpec (missing ones: 0, split_k = batch = mix = 1, c_in_a_col = c_in_b_off = -1).  Returns the whole C buffer after
+        the launch (in place: the aliased operand buffer), and with out0 also beta * out0 + the summed split-k partials."""
+        f = dict(split_k=1, batch=1, mix=1, c_in_a_col=-1, c_in_b_off=-1)
+        f.update(spec)
+        s = GemmSpec(**{k: (float(v) if k in ("alpha", "beta") else int(v)) for k, v in f.items()})
+        A, B = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (A, B))
+        Cb = np.array(C0, dtype=np.float64).ravel()
+        out = None if out0 is None else np.array(out0, dtype=np.float64).ravel()
+        self._check(self.lib.mln_diag_dgemm_run(self.handle, C.byref(s), A.ctypes.data, A.size, B.ctypes.data, B.size,
+                                                Cb.ctypes.data, Cb.size, None if out is None else out.ctypes.data,
+                                                0 if out is None else out.size))
+        return Cb if out is None else (Cb, out)
 
     def gemm(self, A, B, ta=False, tb=False, alpha=1.0, beta=0.0, out=None):
         """out = alpha op(A) op(B) + beta out on the fp64 matrix cores (mln_gemm); A, B, out host arrays or

@@ -230,6 +230,79 @@ extern "C" int mln_diag_dgemm_compare(mln_ctx* ctx, int32_t ta, int32_t tb, int6
   return rc;
 }
 
+// ONE launch of the GEMM on the caller's buffers (tests/gemm_reference.py states what has to come back): every GemmArgs
+// field as given, operands at element offsets into A / B / C (an odd offset or leading dimension takes the scalar loads),
+// C optionally INSIDE the A or B buffer (the in-place panels of linalg.hip).  Every access the spec implies is checked
+// against the element counts first: whole rows of lda / ldb / ldc doubles for every operand row, so a spec that does not fit
+// is MLN_ERR_ARG and never a launch.  C comes back whole, padding included; in place, it receives the aliased buffer.
+extern "C" int mln_diag_dgemm_run(mln_ctx* ctx, const mln_gemm_spec* s, const double* A, int64_t a_count, const double* B,
+                                  int64_t b_count, double* C, int64_t c_count, double* out, int64_t out_count) {
+  if (!ctx || !s || !A || !B || !C) return MLN_ERR_ARG;
+  constexpr int64_t LIM = (int64_t)1 << 20;        // (keeps every product below far from 2^63)
+  auto in = [](int64_t v, int64_t lo, int64_t hi) { return v >= lo && v <= hi; };
+  if (!in(s->ta, 0, 1) || !in(s->tb, 0, 1) || !in(s->M, 1, LIM) || !in(s->N, 1, LIM) || !in(s->K, 1, LIM)) return MLN_ERR_ARG;
+  if (!in(s->lower_only, 0, 3) || !(in(s->kmode, 0, 4) || s->kmode == 7) || !in(s->split_k, 1, 64) || !in(s->batch, 1, 16)) return MLN_ERR_ARG;
+  if (!in(s->lda, 1, LIM) || !in(s->ldb, 1, LIM) || !in(s->ldc, 1, LIM)) return MLN_ERR_ARG;
+  if (!in(s->a_off, 0, LIM) || !in(s->b_off, 0, LIM) || !in(s->c_off, 0, LIM)) return MLN_ERR_ARG;
+  if (!in(a_count, 1, LIM * 64) || !in(b_count, 1, LIM * 64) || !in(c_count, 1, LIM * 64)) return MLN_ERR_ARG;
+  const int64_t nbatch = s->batch, split = s->split_k;
+  const int64_t rows_a = s->ta ? s->K : s->M, cols_a = s->ta ? s->M : s->K;
+  const int64_t rows_b = s->tb ? s->N : s->K, cols_b = s->tb ? s->K : s->N;
+  const bool in_a = s->c_in_a_col >= 0, in_b = s->c_in_b_off >= 0;
+  const int64_t ldc = in_a ? s->lda : (in_b ? s->ldb : s->ldc);
+  if (s->lda < cols_a || s->ldb < cols_b || ldc < s->N) return MLN_ERR_ARG;
+  if (nbatch > 1 && (!in(s->bsa, 0, LIM * 64) || !in(s->bsb, 0, LIM * 64) || !in(s->bsc, split * s->M * ldc, LIM * 64))) return MLN_ERR_ARG;
+  const int64_t bsa = nbatch > 1 ? s->bsa : 0, bsb = nbatch > 1 ? s->bsb : 0, bsc = nbatch > 1 ? s->bsc : 0;
+  if (s->a_off + (nbatch - 1) * bsa + rows_a * s->lda > a_count) return MLN_ERR_ARG;
+  if (s->b_off + (nbatch - 1) * bsb + rows_b * s->ldb > b_count) return MLN_ERR_ARG;
+  int64_t c_rel = 0;      // in place: C relative to the operand it lies in
+  if (in_a || in_b) {
+    if ((in_a && in_b) || split > 1 || nbatch > 1) return MLN_ERR_ARG;
+    const int64_t ld = in_a ? s->lda : s->ldb, rows = in_a ? rows_a : rows_b;
+    c_rel = in_a ? s->c_in_a_col : s->c_in_b_off;
+    if (c_rel % ld + s->N > ld || c_rel + (s->M - 1) * ld + s->N > rows * ld) return MLN_ERR_ARG;
+    if (c_count != (in_a ? a_count : b_count)) return MLN_ERR_ARG;
+  } else if (s->c_off + (nbatch - 1) * bsc + split * s->M * ldc > c_count) {
+    return MLN_ERR_ARG;
+  }
+  const bool summed = s->sum_partials != 0;
+  const int64_t sum_count = s->M * ldc;
+  if (summed && (split < 2 || nbatch > 1 || !out || out_count < sum_count)) return MLN_ERR_ARG;
+  MLN_HIP(ctx, hipSetDevice(ctx->device));
+  DevBuf<double> dA, dB, dC, dO;
+  MLN_TRY(dA.alloc(ctx, (size_t)a_count, "A"));
+  MLN_TRY(dB.alloc(ctx, (size_t)b_count, "B"));
+  MLN_HIP(ctx, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)a_count, hipMemcpyHostToDevice, ctx->stream));
+  MLN_HIP(ctx, hipMemcpyAsync(dB, B, sizeof(double) * (size_t)b_count, hipMemcpyHostToDevice, ctx->stream));
+  if (!in_a && !in_b) {
+    MLN_TRY(dC.alloc(ctx, (size_t)c_count, "C"));
+    MLN_HIP(ctx, hipMemcpyAsync(dC, C, sizeof(double) * (size_t)c_count, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (summed) {
+    MLN_TRY(dO.alloc(ctx, (size_t)out_count, "out"));
+    MLN_HIP(ctx, hipMemcpyAsync(dO, out, sizeof(double) * (size_t)out_count, hipMemcpyHostToDevice, ctx->stream));
+  }
+  GemmArgs g{};
+  g.A = dA + s->a_off; g.lda = s->lda; g.B = dB + s->b_off; g.ldb = s->ldb; g.ldc = ldc;
+  g.C = in_a ? dA + s->a_off + c_rel : (in_b ? dB + s->b_off + c_rel : dC + s->c_off);
+  g.M = s->M; g.N = s->N; g.K = s->K; g.alpha = s->alpha; g.beta = s->beta; g.ta = s->ta; g.tb = s->tb;
+  g.lower_only = s->lower_only; g.kmode = s->kmode; g.split_k = (int)split; g.c_split_stride = s->M * ldc;
+  if (nbatch > 1) { g.batch = (int)nbatch; g.bsa = bsa; g.bsb = bsb; g.bsc = bsc; }
+  dgemm_set_mix(s->mix ? -1 : 0);
+  int rc = launch_dgemm(ctx, g);
+  dgemm_set_mix(-1);
+  if (rc == MLN_OK && summed) rc = launch_sum_partials(ctx, g.C, (int)split, g.c_split_stride, dO, sum_count, s->beta);
+  if (rc == MLN_OK) {
+    double* back = in_a ? dA.get() : (in_b ? dB.get() : dC.get());
+    hipError_t e = hipMemcpyAsync(C, back, sizeof(double) * (size_t)c_count, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && summed) e = hipMemcpyAsync(out, dO, sizeof(double) * (size_t)out_count, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = mln_hip_fail(ctx, e, "dgemm run", __FILE__, __LINE__);
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
 // ---- stream-overlap probe: does a second stream's MFMA-bound GEMM / latency-bound Cholesky run concurrently
 // with the VALU-bound kernel-matrix pass?  out[0..5] = ms: K alone, Gram alone, K||Gram, chol alone, K||chol,
 // and (K_s rows first) is not modelled here.
