@@ -286,6 +286,26 @@ int mln_predict_gradient_multi(mln_ctx* ctx, const mln_kernel_desc* cov, const d
  * here the closed-form second derivatives of the kernels, contracted with the weights on the matrix cores).      */
 int mln_predict_hessian(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new, int32_t d,
                         const double* centers, int64_t m, const double* W /* m */, double* out);
+/* The same for p outputs: out[i][q] = the Hessian of output q at row i.  p == 1 is mln_predict_hessian bit for bit, and so
+ * is, column by column, a call with n_new m < 2^16.  Otherwise, for any program (Linear factors included), the coefficient
+ * matrices are written once per row chunk WITHOUT weights and blocks of outputs are contracted by one GEMM per leaf pair
+ * against W_q [vec(c c'^T) | c | c' | 1], the diagonal term by one GEMM against the weights themselves.  A zero column of W and
+ * inactive dims give exact zeros.                                                                                        */
+int mln_predict_hessian_multi(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new, int32_t d,
+                              const double* centers, int64_t m, const double* W /* m x p, row-major */, int64_t p,
+                              double* out /* n_new x p x d x d */);
+/* numpy.linalg.slogdet of the leading lead x lead block (1 <= lead <= k) of `count` row-major k x k matrices lda >= k k doubles
+ * apart: LU with partial pivoting (ties to the lowest row), sign in {-1, 0, +1}, a singular block gives (0, -inf).  Host or
+ * device pointers.  lead > 64 is MLN_ERR_UNSUPPORTED.  Non-finite entries are outside the contract.                      */
+int mln_slogdet_batched(mln_ctx* ctx, const double* A, int64_t count, int32_t k, int64_t lda, int32_t lead,
+                        double* sign /* count */, double* logabsdet /* count */);
+/* mln_predict_hessian_multi followed by mln_slogdet_batched without the Hessians leaving the device (they are built and
+ * factored per row chunk and block of outputs in scratch): Predictor.hessian_log_determinant (base_predictor.py:523-539;
+ * lead = d) and PredictorTime's (1162-1194; lead = d - 1, the state columns).  The Hessians factored are, bit for bit,
+ * those mln_predict_hessian_multi returns.                                                                             */
+int mln_predict_hessian_logdet(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new, int32_t d,
+                               const double* centers, int64_t m, const double* W /* m x p, row-major */, int64_t p,
+                               int32_t lead, double* sign /* n_new x p */, double* logabsdet /* n_new x p */);
 
 /* ---- derivatives of block-evaluated covariance trees (more than MLN_MAX_LEAVES leaves, a deeper stack, user-defined
  * leaves; base_cov.py:317-497, base_predictor.py:490-539).  The binding walks the tree per row block and carries every

@@ -86,6 +86,9 @@ SYMBOLS = [
     ("mln_predict_gradient", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp]),
     ("mln_predict_gradient_multi", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dp]),
     ("mln_predict_hessian", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp]),
+    ("mln_predict_hessian_multi", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dp]),
+    ("mln_slogdet_batched", C.c_int, [_vp, _dp, _i64, _i32, _i64, _i32, _dp, _dp]),
+    ("mln_predict_hessian_logdet", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _i32, _dp, _dp]),
     ("mln_leaf_factors", C.c_int, [_vp, _KD, _dp, _i64, _dp, _i64, _i32, _i32, _i64, _dp, _dp, _dp]),
     ("mln_block_grad_accumulate", C.c_int, [_vp, C.POINTER(Leaf), _i32, C.POINTER(_vp), _i64, _dp, _i64, _i32, _dp, _i64,
                                             _dp, _dp]),
@@ -455,20 +458,69 @@ class Context:
         return K, g
 
     def predict_hessian(self, desc, xnew, centers, W):
-        """Hessian of the predictive mean at each query point: (n_new, d, d)."""
+        """Hessian of the predictive mean at each query point: (n_new, d, d) for weights of shape (m,), (n_new, p, d, d) for
+        (m, p) -- every output in one device call (mln_predict_hessian_multi)."""
         xnew = xnew if isinstance(xnew, DeviceArray) else _as2d(xnew)
         centers = centers if isinstance(centers, DeviceArray) else _as2d(centers)
         Wd = _f64(W)
-        if Wd.ndim != 1 or Wd.shape[0] != centers.shape[0]:
-            raise NotImplementedError("hessians are available for single-output predictors (weights of shape (m,))")
+        if Wd.ndim not in (1, 2) or Wd.shape[0] != centers.shape[0]:
+            raise ValueError(f"weights of shape {Wd.shape} do not go with {centers.shape[0]} centres: (m,) or (m, p)")
         if isinstance(desc, BlockEvaluatedCov):          # a tree that is not one device program
             from . import block_derivatives
+            if Wd.ndim == 2:
+                return np.stack([block_derivatives.predict_hessian(self, desc, xnew, centers, np.ascontiguousarray(Wd[:, q]))
+                                 for q in range(Wd.shape[1])], axis=1)
             return block_derivatives.predict_hessian(self, desc, xnew, centers, Wd)
         n_new, d = xnew.shape
+        if Wd.ndim == 2:
+            p = Wd.shape[1]
+            out = np.empty((n_new, p, d, d), dtype=np.float64)
+            if p:
+                self._check(self.lib.mln_predict_hessian_multi(self.handle, desc.ref, _ptr(xnew), n_new, d, _ptr(centers),
+                                                               centers.shape[0], Wd.ctypes.data, p, out.ctypes.data))
+            return out
         out = np.empty((n_new, d, d), dtype=np.float64)
         self._check(self.lib.mln_predict_hessian(self.handle, desc.ref, _ptr(xnew), n_new, d, _ptr(centers),
                                                  centers.shape[0], Wd.ctypes.data, out.ctypes.data))
         return out
+
+    SLOGDET_MAX_LEAD = 64         # blocks the device factors (one wavefront per matrix); above it NotImplementedError
+
+    def slogdet_batched(self, A, lead=None):
+        """(sign, logabsdet) of the leading lead x lead block (default: all) of every k x k matrix of A, an array of shape
+        (..., k, k) -- numpy.linalg.slogdet's conventions, (0, -inf) for a singular block (mln_slogdet_batched)."""
+        A = _f64(A)
+        if A.ndim < 2 or A.shape[-1] != A.shape[-2] or A.shape[-1] < 1:
+            raise ValueError(f"slogdet_batched needs an array of shape (..., k, k), got {A.shape}")
+        k = A.shape[-1]
+        lead = k if lead is None else int(lead)
+        batch = A.shape[:-2]
+        count = int(np.prod(batch, dtype=np.int64))
+        sign, logabs = np.empty(batch, dtype=np.float64), np.empty(batch, dtype=np.float64)
+        self._check(self.lib.mln_slogdet_batched(self.handle, A.ctypes.data, count, k, k * k, lead, sign.ctypes.data,
+                                                 logabs.ctypes.data))
+        return sign, logabs
+
+    def predict_hessian_logdet(self, desc, xnew, centers, W, lead=None):
+        """(sign, logabsdet) of the leading lead x lead block (default: d) of the Hessian of the predictive mean at each
+        query point, (n_new,) each for weights (m,) and (n_new, p) for (m, p): predict_hessian and slogdet_batched in one
+        device call, the Hessians never leave the device (mln_predict_hessian_logdet)."""
+        _needs_program(desc, "predict_hessian_logdet")
+        xnew = xnew if isinstance(xnew, DeviceArray) else _as2d(xnew)
+        centers = centers if isinstance(centers, DeviceArray) else _as2d(centers)
+        Wd = _f64(W)
+        if Wd.ndim not in (1, 2) or Wd.shape[0] != centers.shape[0]:
+            raise ValueError(f"weights of shape {Wd.shape} do not go with {centers.shape[0]} centres: (m,) or (m, p)")
+        n_new, d = xnew.shape
+        lead = d if lead is None else int(lead)
+        p = Wd.shape[1] if Wd.ndim == 2 else 1
+        shape = (n_new, p) if Wd.ndim == 2 else (n_new,)
+        sign, logabs = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.float64)
+        if p:
+            self._check(self.lib.mln_predict_hessian_logdet(self.handle, desc.ref, _ptr(xnew), n_new, d, _ptr(centers),
+                                                            centers.shape[0], Wd.ctypes.data, p, lead, sign.ctypes.data,
+                                                            logabs.ctypes.data))
+        return sign, logabs
 
     def nn_distances(self, x, y=None, self_offset=0):
         """Exact nearest-neighbour distance of each row of x among the rows of y (default: x itself)."""

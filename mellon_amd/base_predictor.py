@@ -150,13 +150,30 @@ class Predictor:
         with the weights on the device.  `jit` is accepted and ignored."""
         x = self._check_features(x)
         ctx, desc = _lib.default_context(), self.cov_func.lower(self.n_input_features)
-        if self.weights.ndim == 2:      # p outputs: (n, p, d, d) (derivatives.py:114-117)
-            return np.stack([ctx.predict_hessian(desc, x, self.centers, np.ascontiguousarray(self.weights[:, c]))
-                             for c in range(self.weights.shape[1])], axis=1)
+        # p outputs: (n, p, d, d), the layout derivatives.hessian gives (derivatives.py:114-117), in one device call
         return ctx.predict_hessian(desc, x, self.centers, self.weights)
 
+    _LOGDET_MIN_PAIRS = 1 << 16      # n_new m from which the Hessians are factored on the device (the GEMM routes' threshold)
+
+    def _device_hessian_logdet(self, x, lead):
+        """(signs, log |det|) of the leading lead x lead blocks of the Hessians of `Predictor.hessian` at the validated
+        rows x, from the fused device entry -- or None where the host path has to run: a tree that is not one device
+        program, a block the device does not factor, fewer than _LOGDET_MIN_PAIRS pairs (there the host path keeps its
+        bits)."""
+        ctx, desc = _lib.default_context(), self.cov_func.lower(self.n_input_features)
+        if (isinstance(desc, _lib.BlockEvaluatedCov) or not 1 <= lead <= ctx.SLOGDET_MAX_LEAD
+                or x.shape[0] * self.centers.shape[0] < self._LOGDET_MIN_PAIRS):
+            return None
+        return ctx.predict_hessian_logdet(desc, x, self.centers, self.weights, lead=lead)
+
     def hessian_log_determinant(self, x, jit=True):
-        """(signs, log |det|) of the Hessian at each row of x (base_predictor.py:523-539)."""
+        """(signs, log |det|) of the Hessian at each row of x (base_predictor.py:523-539).  From 2^16 (query, centre) pairs
+        on the Hessians are built and factored on the device and only the two results come back; a subclass with a
+        `hessian` of its own (ExpPredictor) gets numpy's slogdet of that."""
+        if type(self).hessian is Predictor.hessian:
+            fused = self._device_hessian_logdet(self._check_features(x), self.n_input_features)
+            if fused is not None:
+                return fused
         sign, logdet = np.linalg.slogdet(self.hessian(x))
         return sign, logdet
 
@@ -320,8 +337,12 @@ class PredictorTime(Predictor):
 
     @make_multi_time_argument
     def hessian_log_determinant(self, x, time=None, jit=True):
-        """base_predictor.py:1162-1194."""
-        sign, logdet = np.linalg.slogdet(Predictor.hessian(self, self._with_time(x, time))[..., :-1, :-1])
+        """base_predictor.py:1162-1194.  The state columns are the leading (d - 1) x (d - 1) block of the full Hessian."""
+        x = self._with_time(x, time)
+        fused = self._device_hessian_logdet(x, self.n_input_features - 1)
+        if fused is not None:
+            return fused
+        sign, logdet = np.linalg.slogdet(Predictor.hessian(self, x)[..., :-1, :-1])
         return sign, logdet
 
     @make_multi_time_argument
@@ -373,6 +394,38 @@ class PredictorTime(Predictor):
             return NotImplemented
         state, Xq, E, _ = setup
         return np.ascontiguousarray(_lib.default_context().predict_gradient(state, Xq, self.centers, E)[..., :-1])
+
+    # hess_x[i, t] = the T-output Hessian of the state kernel with weights E, its leading (d - 1) x (d - 1) block.  The device
+    # call returns (n, T_b, d, d) with the time row and column; times go in blocks of T_b so that one call's result stays
+    # within _GRID_HESSIAN_DOUBLES, and each block's state columns are copied into the (n, T, d - 1, d - 1) result.
+    _GRID_HESSIAN_DOUBLES = 1 << 28      # 2 GiB of host memory per device call
+
+    def _grid_hessian(self, x, time=None, jit=True, times=None):
+        setup = self._grid_setup(x, times)
+        if setup is None:
+            return NotImplemented
+        state, Xq, E, _ = setup
+        ctx = _lib.default_context()
+        n, d = Xq.shape
+        T = times.shape[0]
+        tb = max(1, self._GRID_HESSIAN_DOUBLES // max(1, n * d * d))
+        if tb >= T:
+            return np.ascontiguousarray(ctx.predict_hessian(state, Xq, self.centers, E)[..., :-1, :-1])
+        out = np.empty((n, T, d - 1, d - 1), dtype=np.float64)
+        for t0 in range(0, T, tb):
+            out[:, t0:t0 + tb] = ctx.predict_hessian(state, Xq, self.centers,
+                                                     np.ascontiguousarray(E[:, t0:t0 + tb]))[..., :-1, :-1]
+        return out
+
+    def _grid_hessian_log_determinant(self, x, time=None, jit=True, times=None):
+        lead = self.n_input_features - 1
+        if not 1 <= lead <= _lib.Context.SLOGDET_MAX_LEAD:
+            return NotImplemented                  # the loop's host path factors what the device does not
+        setup = self._grid_setup(x, times)
+        if setup is None:
+            return NotImplemented
+        state, Xq, E, _ = setup
+        return _lib.default_context().predict_hessian_logdet(state, Xq, self.centers, E, lead=lead)
 
     def _grid_time_derivative(self, x, time=None, jit=True, times=None):
         setup = self._grid_setup(x, times, want_derivative=True)

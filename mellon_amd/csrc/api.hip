@@ -323,6 +323,78 @@ extern "C" int mln_predict_hessian(mln_ctx* ctx, const mln_kernel_desc* cov, con
   return o.commit();
 }
 
+extern "C" int mln_predict_hessian_multi(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new,
+                                         int32_t d, const double* centers, int64_t m, const double* W, int64_t p,
+                                         double* out) {
+  if (!ctx) return MLN_ERR_ARG;
+  if (n_new < 0 || m < 1 || d < 1 || p < 1) { mln_set_error(ctx, "bad shape"); return MLN_ERR_SHAPE; }
+  if (n_new == 0) return MLN_OK;
+  if (!xnew || !out || !centers || !W) return MLN_ERR_ARG;
+  MLN_HIP(ctx, hipSetDevice(ctx->device));
+  DevCov dc;
+  MLN_TRY(mln_lower_cov(ctx, cov, d, &dc));
+  MLN_TRY(reject_distance_leaf(ctx, dc));
+  DevIn dx, dc_, dw;
+  DevOut o;
+  MLN_TRY(dx.init(ctx, xnew, (size_t)n_new * d));
+  MLN_TRY(dc_.init(ctx, centers, (size_t)m * d));
+  MLN_TRY(dw.init(ctx, W, (size_t)m * (size_t)p));
+  MLN_TRY(o.init(ctx, out, (size_t)n_new * (size_t)p * d * d));
+  MLN_TRY(launch_predict_hessian_multi(ctx, dc, dx.dev, n_new, dc_.dev, m, d, dw.dev, p, o.dev));
+  return o.commit();
+}
+
+static int check_lead(mln_ctx* ctx, int32_t lead, int32_t k) {
+  if (lead < 1 || lead > k) { mln_set_error(ctx, "the leading block must be 1 .. k"); return MLN_ERR_SHAPE; }
+  if (lead > SLOGDET_MAX_LEAD) {
+    mln_set_error(ctx, "slogdet on the device factors blocks of at most 64 x 64");
+    return MLN_ERR_UNSUPPORTED;
+  }
+  return MLN_OK;
+}
+
+extern "C" int mln_slogdet_batched(mln_ctx* ctx, const double* A, int64_t count, int32_t k, int64_t lda, int32_t lead,
+                                   double* sign, double* logabsdet) {
+  if (!ctx) return MLN_ERR_ARG;
+  if (count < 0 || k < 1 || lda < (int64_t)k * k) { mln_set_error(ctx, "bad shape"); return MLN_ERR_SHAPE; }
+  MLN_TRY(check_lead(ctx, lead, k));
+  if (count == 0) return MLN_OK;
+  if (!A || !sign || !logabsdet) return MLN_ERR_ARG;
+  MLN_HIP(ctx, hipSetDevice(ctx->device));
+  DevIn da;
+  DevOut os, ol;
+  MLN_TRY(da.init(ctx, A, (size_t)(count - 1) * (size_t)lda + (size_t)k * k));
+  MLN_TRY(os.init(ctx, sign, (size_t)count));
+  MLN_TRY(ol.init(ctx, logabsdet, (size_t)count));
+  MLN_TRY(launch_slogdet_batched(ctx, da.dev, count, k, lda, lead, os.dev, ol.dev, 1, 1, 0));
+  MLN_TRY(os.commit());
+  return ol.commit();
+}
+
+extern "C" int mln_predict_hessian_logdet(mln_ctx* ctx, const mln_kernel_desc* cov, const double* xnew, int64_t n_new,
+                                          int32_t d, const double* centers, int64_t m, const double* W, int64_t p,
+                                          int32_t lead, double* sign, double* logabsdet) {
+  if (!ctx) return MLN_ERR_ARG;
+  if (n_new < 0 || m < 1 || d < 1 || p < 1) { mln_set_error(ctx, "bad shape"); return MLN_ERR_SHAPE; }
+  MLN_TRY(check_lead(ctx, lead, d));
+  if (n_new == 0) return MLN_OK;
+  if (!xnew || !sign || !logabsdet || !centers || !W) return MLN_ERR_ARG;
+  MLN_HIP(ctx, hipSetDevice(ctx->device));
+  DevCov dc;
+  MLN_TRY(mln_lower_cov(ctx, cov, d, &dc));
+  MLN_TRY(reject_distance_leaf(ctx, dc));
+  DevIn dx, dc_, dw;
+  DevOut os, ol;
+  MLN_TRY(dx.init(ctx, xnew, (size_t)n_new * d));
+  MLN_TRY(dc_.init(ctx, centers, (size_t)m * d));
+  MLN_TRY(dw.init(ctx, W, (size_t)m * (size_t)p));
+  MLN_TRY(os.init(ctx, sign, (size_t)n_new * (size_t)p));
+  MLN_TRY(ol.init(ctx, logabsdet, (size_t)n_new * (size_t)p));
+  MLN_TRY(launch_predict_hessian_logdet(ctx, dc, dx.dev, n_new, dc_.dev, m, d, dw.dev, p, lead, os.dev, ol.dev));
+  MLN_TRY(os.commit());
+  return ol.commit();
+}
+
 
 // G (m x m) = cov(x, xu)^T cov(x, xu): the B^T B of the landmark leverage (conditional.py:660-685) without
 // the n x m matrix leaving the device; rows in chunks, all-reduced over ranks.

@@ -16,6 +16,7 @@
 #include "cov_leaf.h"
 #include "cov_rows.h"
 #include "mln_options.h"
+#include "linalg.h"
 
 namespace {
 
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(256) void k_hess_coeff(DevCov cov, const double* __
         hc[l] = leaf_hess_coeff(lf, xr[l][i], yr[l][j], acc[l][i][j]);
       }
       program_second(cov, kv, a1, a2);
-      const double wc = (c < m) ? w[c] : 0.0;
+      const double wc = (c < m) ? (w ? w[c] : 1.0) : 0.0;   // w == nullptr: the coefficients alone (1.0 * v is v exactly)
       const int64_t at = r * ldo + c;
 #pragma unroll
       for (int l = 0; l < MLN_MAX_LEAVES; ++l) {
@@ -488,6 +489,71 @@ __global__ __launch_bounds__(256) void k_hess_diag(DevCov cov, int l, const doub
     const int dim = cov.dims[lf.dims_off + k];
     H[i * (int64_t)d * d + (int64_t)dim * d + dim] += red[0];
   }
+}
+
+// ---- predictor Hessian for p outputs (hessian_batched): k_hess_coeff runs WITHOUT weights, the weights move into the
+// centre operands, pb outputs side by side (ncol = na nb + na + nb + 1 columns each):
+//   Z[j][q ncol + k] = W[j][q0 + q] Cp_ll'[j][k]   (Cp: k_hess_centres), zero up to ldz
+__global__ void k_hess_weighted_centres(DevCov cov, int l, int lp, const double* __restrict__ c, int64_t m, int d,
+                                        const double* __restrict__ W, int64_t p, int64_t q0, int64_t pb,
+                                        double* __restrict__ Z, int64_t ldz) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= m * ldz) return;
+  const DevLeaf la = cov.leaves[l], lb = cov.leaves[lp];
+  const int na = la.ndims, nb = lb.ndims, ncol = na * nb + na + nb + 1;
+  const int64_t j = idx / ldz, col = idx % ldz, q = col / ncol;
+  const int k = (int)(col % ncol);
+  double v = 0.0;
+  if (q < pb) {
+    const double* cj = c + j * d;
+    v = W[j * p + q0 + q];
+    if (k < na * nb) v *= cj[cov.dims[la.dims_off + k / nb]] * cj[cov.dims[lb.dims_off + k % nb]];
+    else if (k < na * nb + na) v *= cj[cov.dims[la.dims_off + (k - na * nb)]];
+    else if (k < na * nb + na + nb) v *= cj[cov.dims[lb.dims_off + (k - na * nb - na)]];
+  }
+  Z[idx] = v;
+}
+
+// Z[j][q] = W[j][q0 + q] (q < pb), zero up to ldz: the operand of the diagonal term's GEMM
+__global__ void k_hess_weight_block(const double* __restrict__ W, int64_t m, int64_t p, int64_t q0, int64_t pb,
+                                    double* __restrict__ Z, int64_t ldz) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= m * ldz) return;
+  const int64_t j = idx / ldz, q = idx % ldz;
+  Z[idx] = (q < pb) ? W[j * p + q0 + q] : 0.0;
+}
+
+// k_hess_combine with an output index: H is rows x ph x d x d, output q of the block goes to H[i][qoff + q]; T holds the
+// block's pb outputs side by side (ncol columns each)
+__global__ void k_hess_combine_outputs(DevCov cov, int l, int lp, int transpose, const double* __restrict__ T, int64_t ldt,
+                                       const double* __restrict__ x, int64_t rows, int d, int64_t ph, int64_t qoff,
+                                       int64_t pb, double* __restrict__ H) {
+  const DevLeaf la = cov.leaves[l], lb = cov.leaves[lp];
+  const int na = la.ndims, nb = lb.ndims;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * pb * na * nb) return;
+  const int ab = (int)(idx % (na * nb)), a = ab / nb, b = ab % nb;
+  const int64_t q = (idx / (na * nb)) % pb, i = idx / ((int64_t)na * nb * pb);
+  const int da = cov.dims[la.dims_off + a], db = cov.dims[lb.dims_off + b];
+  const double sa = (la.kind == MLN_K_LINEAR) ? 0.0 : 1.0, sb = (lb.kind == MLN_K_LINEAR) ? 0.0 : 1.0;
+  const double* Ti = T + i * ldt + q * (na * nb + na + nb + 1);
+  const double xa = x[i * d + da], xb = x[i * d + db];
+  const double val = sa * sb * Ti[na * nb + na + nb] * xa * xb - sa * xa * Ti[na * nb + na + b]
+                     - sb * Ti[na * nb + a] * xb + Ti[ab];
+  double* Hi = H + (i * ph + qoff + q) * (int64_t)d * d;
+  if (transpose) Hi[db * d + da] += val; else Hi[da * d + db] += val;
+}
+
+// H[i][qoff + q][dim][dim] += Td[i][q] for the dims of one stationary leaf (Td = Qd_l W_block: k_hess_diag's row sum as a GEMM)
+__global__ void k_hess_diag_outputs(DevCov cov, int l, const double* __restrict__ Td, int64_t ldt, int64_t rows, int d,
+                                    int64_t ph, int64_t qoff, int64_t pb, double* __restrict__ H) {
+  const DevLeaf lf = cov.leaves[l];
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * pb * lf.ndims) return;
+  const int k = (int)(idx % lf.ndims);
+  const int64_t q = (idx / lf.ndims) % pb, i = idx / ((int64_t)lf.ndims * pb);
+  const int dim = cov.dims[lf.dims_off + k];
+  H[(i * ph + qoff + q) * (int64_t)d * d + (int64_t)dim * d + dim] += Td[i * ldt + q];
 }
 
 // mean_i = mu + sum_j cov(x_i, y_j) w_j   (conditional.py:899-906); K never leaves registers.
@@ -1026,6 +1092,15 @@ int launch_row_sumsq(mln_ctx* ctx, const double* T, int64_t ld, int64_t rows, in
 }
 
 
+// rows per chunk of launch_predict_hessian before it is clamped to n: <= 2 GiB of coefficient matrices per chunk
+static int64_t hess_single_chunk(int L, int64_t m) {
+  const int64_t ldq = ((m + 15) / 16) * 16;
+  int64_t chunk = ((int64_t)1 << 28) / (ldq * (L + (L * (L + 1)) / 2));
+  if (chunk > 16384) chunk = 16384;
+  if (chunk < 64) chunk = 64;
+  return chunk;
+}
+
 // Hessian of the predicted mean at every row of x (see k_hess_coeff): out is n x d x d.
 int launch_predict_hessian(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
                            int d, const double* w, double* out) {
@@ -1033,9 +1108,7 @@ int launch_predict_hessian(mln_ctx* ctx, const DevCov& cov, const double* x, int
   const int L = cov.n_leaves;
   const int n_slots = L + (L * (L + 1)) / 2;
   const int64_t ldq = ((m + 15) / 16) * 16;
-  int64_t chunk = ((int64_t)1 << 28) / (ldq * n_slots);        // <= 2 GiB of coefficient matrices per chunk
-  if (chunk > 16384) chunk = 16384;
-  if (chunk < 64) chunk = 64;
+  int64_t chunk = hess_single_chunk(L, m);
   if (chunk > n) chunk = n;
   // centre operands of the pair GEMMs
   std::vector<int64_t> cp_off((size_t)L * L, 0), cp_ld((size_t)L * L, 0);
@@ -1098,6 +1171,162 @@ int launch_predict_hessian(mln_ctx* ctx, const DevCov& cov, const double* x, int
   (void)hipStreamSynchronize(ctx->stream);
   if (rc == MLN_OK && e != hipSuccess) rc = mln_hip_fail(ctx, e, "predict_hessian", __FILE__, __LINE__);
   return rc;
+}
+
+// ---- Hessians of p outputs (W m x p row-major; out n x p x d x d) and their sign / log|det| --------------------------------
+//   p == 1                     launch_predict_hessian itself
+//   n m < 2^16                 launch_predict_hessian per column (gathered weights, scattered result): its bits
+//   anything else, any program (a Linear factor is sig = 0 inside the same GEMM formulation)   hessian_batched:
+//     per row chunk:  k_hess_coeff with a null weight pointer                  ONE covariance-tile pass, whatever p is
+//     per output block [q0, q0 + pb), per stationary leaf:  Td = Qd_l W[:, q0 .. q0 + pb)     the diagonal term, pb columns
+//                                     per leaf pair:        T = Qp_ll' Z_ll'                  pb ncol_ll' columns
+//                                                           out[:, q0 + q] += the expansion of k_hess_combine
+// pb ncol_max <= HESS_MULTI_COLS columns per GEMM (MELLON_AMD_HESS_COLS overrides it, read at every call).  Rows per chunk: a
+// multiple of 64, at most 16384 (launch_predict_hessian's cap), never below 64, and Q (n_slots ldq per row) plus T (ldz per row)
+// plus one output block of Hessians (pb d^2 per row) within HESS_MULTI_SCRATCH doubles.  The Hessian block counts in BOTH
+// entries although only the fused one (launch_predict_hessian_logdet) allocates it: the two then issue the same launches on
+// the same rows, so the fused entry factors exactly the bits launch_predict_hessian_multi returns.
+constexpr int64_t HESS_MULTI_COLS = 4096;
+constexpr int64_t HESS_MULTI_SCRATCH = (int64_t)1 << 28;   // 2 GiB of doubles
+constexpr int64_t HESS_MULTI_MIN_PAIRS = (int64_t)1 << 16;
+
+// out != nullptr: the Hessians; out == nullptr: sign / logabs (n x p) of their leading lead x lead blocks
+static int hessian_batched(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m, int d,
+                           const double* W, int64_t p, double* out, int lead, double* sign, double* logabs) {
+  const int L = cov.n_leaves;
+  const int n_slots = L + (L * (L + 1)) / 2;
+  int64_t ncol_max = 1;
+  for (int l = 0; l < L; ++l)
+    for (int lp = l; lp < L; ++lp) {
+      const int64_t na = cov.leaves[l].ndims, nb = cov.leaves[lp].ndims, ncol = na * nb + na + nb + 1;
+      if (ncol > ncol_max) ncol_max = ncol;
+    }
+  int64_t cols = HESS_MULTI_COLS;
+  if (const char* e = std::getenv("MELLON_AMD_HESS_COLS")) {
+    const long long v = std::atoll(e);
+    if (v >= 1 && v <= 65536) cols = v;
+  }
+  int64_t pb_max = cols / ncol_max;
+  if (pb_max < 1) pb_max = 1;
+  if (pb_max > p) pb_max = p;
+  const int64_t ldq = ((m + 15) / 16) * 16, ldz = ((pb_max * ncol_max + 15) / 16) * 16;
+  const int64_t dd = (int64_t)d * d;
+  int64_t chunk = HESS_MULTI_SCRATCH / ((int64_t)n_slots * ldq + ldz + pb_max * dd);
+  chunk = (chunk / 64) * 64;
+  if (chunk > 16384) chunk = 16384;
+  if (chunk < 64) chunk = 64;
+  if (chunk > n) chunk = n;
+  double* norms = nullptr;
+  DevBuf<double> Q, T, Z, Hs;
+  MLN_TRY(mln_scratch(ctx, sizeof(double) * (size_t)L * (size_t)(n + m), (void**)&norms));
+  double* xx = norms;
+  double* yy = norms + (size_t)L * n;
+  MLN_TRY(sqnorms(ctx, cov, x, n, d, xx));
+  MLN_TRY(sqnorms(ctx, cov, c, m, d, yy));
+  const int64_t slot_stride = chunk * ldq;
+  MLN_TRY(Q.alloc(ctx, (size_t)n_slots * slot_stride, "Q"));
+  MLN_TRY(T.alloc(ctx, (size_t)chunk * ldz, "T"));
+  MLN_TRY(Z.alloc(ctx, (size_t)m * ldz, "Z"));
+  if (out) MLN_HIP(ctx, hipMemsetAsync(out, 0, sizeof(double) * (size_t)n * (size_t)p * dd, ctx->stream));
+  else MLN_TRY(Hs.alloc(ctx, (size_t)chunk * pb_max * dd, "Hs"));
+  int rc = MLN_OK;
+  const int64_t tiles_n = (ldq + TN - 1) / TN;
+  const unsigned zblocks = (unsigned)((m * ldz + 255) / 256);
+  for (int64_t r0 = 0; r0 < n && rc == MLN_OK; r0 += chunk) {
+    const int64_t rows = (n - r0 < chunk) ? (n - r0) : chunk;
+    const int64_t nblk = tiles_n * ((rows + TM - 1) / TM);
+    const double* xc = x + r0 * d;
+    hipLaunchKernelGGL(k_hess_coeff, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, cov, xc, rows, c, m, d, xx + r0, n, yy,
+                       (const double*)nullptr, Q.get(), ldq, slot_stride, tiles_n);
+    for (int64_t q0 = 0; q0 < p && rc == MLN_OK; q0 += pb_max) {
+      const int64_t pb = (p - q0 < pb_max) ? (p - q0) : pb_max;
+      double* H = out ? out + r0 * p * dd : Hs.get();
+      const int64_t ph = out ? p : pb, qoff = out ? q0 : 0;
+      if (!out) {
+        const hipError_t em = hipMemsetAsync(H, 0, sizeof(double) * (size_t)(rows * pb * dd), ctx->stream);
+        if (em != hipSuccess) { rc = mln_hip_fail(ctx, em, "predict_hessian_logdet", __FILE__, __LINE__); break; }
+      }
+      for (int l = 0; l < L && rc == MLN_OK; ++l) {
+        const int na = cov.leaves[l].ndims;
+        if (na == 0) continue;
+        if (cov.leaves[l].kind != MLN_K_LINEAR) {
+          hipLaunchKernelGGL(k_hess_weight_block, dim3(zblocks), dim3(256), 0, ctx->stream, W, m, p, q0, pb, Z.get(), ldz);
+          GemmArgs g{};
+          g.A = Q + (size_t)l * slot_stride; g.lda = ldq; g.ta = 0; g.B = Z; g.ldb = ldz; g.tb = 0; g.C = T; g.ldc = ldz;
+          g.M = rows; g.N = pb; g.K = m; g.alpha = 1.0; g.beta = 0.0; g.split_k = 1;
+          rc = launch_dgemm(ctx, g);
+          if (rc != MLN_OK) break;
+          hipLaunchKernelGGL(k_hess_diag_outputs, dim3((unsigned)((rows * pb * na + 255) / 256)), dim3(256), 0, ctx->stream,
+                             cov, l, T.get(), ldz, rows, d, ph, qoff, pb, H);
+        }
+        for (int lp = l; lp < L && rc == MLN_OK; ++lp) {
+          const int nb = cov.leaves[lp].ndims;
+          if (nb == 0) continue;
+          hipLaunchKernelGGL(k_hess_weighted_centres, dim3(zblocks), dim3(256), 0, ctx->stream, cov, l, lp, c, m, d, W, p, q0,
+                             pb, Z.get(), ldz);
+          GemmArgs g{};
+          g.A = Q + (size_t)hess_pair_slot(L, l, lp) * slot_stride; g.lda = ldq; g.ta = 0; g.B = Z; g.ldb = ldz; g.tb = 0;
+          g.C = T; g.ldc = ldz; g.M = rows; g.N = pb * ((int64_t)na * nb + na + nb + 1); g.K = m; g.alpha = 1.0; g.beta = 0.0;
+          g.split_k = 1;
+          rc = launch_dgemm(ctx, g);
+          if (rc != MLN_OK) break;
+          const unsigned nb_ = (unsigned)((rows * pb * na * nb + 255) / 256);
+          hipLaunchKernelGGL(k_hess_combine_outputs, dim3(nb_), dim3(256), 0, ctx->stream, cov, l, lp, 0, T.get(), ldz, xc,
+                             rows, d, ph, qoff, pb, H);
+          if (lp != l)
+            hipLaunchKernelGGL(k_hess_combine_outputs, dim3(nb_), dim3(256), 0, ctx->stream, cov, l, lp, 1, T.get(), ldz, xc,
+                               rows, d, ph, qoff, pb, H);
+        }
+      }
+      if (!out && rc == MLN_OK)
+        rc = launch_slogdet_batched(ctx, H, rows * pb, d, dd, lead, sign + r0 * p, logabs + r0 * p, pb, p, q0);
+    }
+  }
+  hipError_t e = hipGetLastError();
+  (void)hipStreamSynchronize(ctx->stream);
+  if (rc == MLN_OK && e != hipSuccess) rc = mln_hip_fail(ctx, e, "predict_hessian_multi", __FILE__, __LINE__);
+  return rc;
+}
+
+int launch_predict_hessian_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
+                                 int d, const double* W, int64_t p, double* out) {
+  if (n == 0 || p == 0) return MLN_OK;
+  if (p == 1) return launch_predict_hessian(ctx, cov, x, n, c, m, d, W, out);
+  if (n * m >= HESS_MULTI_MIN_PAIRS) return hessian_batched(ctx, cov, x, n, c, m, d, W, p, out, 0, nullptr, nullptr);
+  const int64_t dd = (int64_t)d * d;
+  DevBuf<double> wq, hq;
+  MLN_TRY(wq.alloc(ctx, (size_t)m, "wq"));
+  MLN_TRY(hq.alloc(ctx, (size_t)n * dd, "hq"));
+  for (int64_t q = 0; q < p; ++q) {      // (fewer than 2^16 pairs: the copies are a few thousand doubles)
+    MLN_TRY(launch_copy_block(ctx, W + q, p, wq.get(), 1, m, 1));
+    MLN_TRY(launch_predict_hessian(ctx, cov, x, n, c, m, d, wq.get(), hq.get()));
+    MLN_TRY(launch_copy_block(ctx, hq.get(), dd, out + q * dd, p * dd, n, dd));
+  }
+  MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MLN_OK;
+}
+
+// sign / logabs (n x p) of the leading lead x lead block of every Hessian: only these reach the caller.  The batched route
+// factors each (row chunk, output block) in scratch; the single-output routes run on row blocks that are whole multiples of
+// launch_predict_hessian's own chunk (the launches, hence the bits, of the unfused call), within HESS_MULTI_SCRATCH doubles
+// of Hessians where one such chunk allows.
+int launch_predict_hessian_logdet(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
+                                  int d, const double* W, int64_t p, int lead, double* sign, double* logabs) {
+  if (n == 0 || p == 0) return MLN_OK;
+  if (p > 1 && n * m >= HESS_MULTI_MIN_PAIRS) return hessian_batched(ctx, cov, x, n, c, m, d, W, p, nullptr, lead, sign, logabs);
+  const int64_t dd = (int64_t)d * d, step = hess_single_chunk(cov.n_leaves, m);
+  int64_t rb = (HESS_MULTI_SCRATCH / (p * dd)) / step * step;
+  if (rb < step) rb = step;
+  if (rb > n) rb = n;
+  DevBuf<double> Hs;
+  MLN_TRY(Hs.alloc(ctx, (size_t)rb * p * dd, "Hs"));
+  for (int64_t r0 = 0; r0 < n; r0 += rb) {
+    const int64_t rows = (n - r0 < rb) ? (n - r0) : rb;
+    MLN_TRY(launch_predict_hessian_multi(ctx, cov, x + r0 * d, rows, c, m, d, W, p, Hs.get()));
+    MLN_TRY(launch_slogdet_batched(ctx, Hs.get(), rows * p, d, dd, lead, sign + r0 * p, logabs + r0 * p, 1, 1, 0));
+  }
+  MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MLN_OK;
 }
 
 // Predictor gradient of a composite program of stationary leaves through the matrix cores (see k_grad_coeff_multi).

@@ -94,6 +94,20 @@ int launch_predict_gradient_batched(mln_ctx* ctx, const DevCov& cov, const doubl
 int launch_predict_gradient_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
                                   int d, const double* W, int64_t p, double* out);
 
+// Hessians of p outputs, W m x p row-major, out n x p x d x d (cov_kernels.hip): p == 1 and fewer than 2^16 pairs go through
+// launch_predict_hessian (per column), the rest through one weight-less coefficient pass per row chunk and GEMMs over blocks of
+// outputs.  _logdet: the same Hessians built in scratch and factored there -- only sign / logabs (n x p each) are written.
+int launch_predict_hessian_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
+                                 int d, const double* W, int64_t p, double* out);
+int launch_predict_hessian_logdet(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
+                                  int d, const double* W, int64_t p, int lead, double* sign, double* logabs);
+
+// slogdet.hip: sign and log|det| of the leading lead x lead block of `count` k x k matrices lda doubles apart; result idx is
+// written at [(idx / inner) out_stride + out_off + idx % inner]
+constexpr int SLOGDET_MAX_LEAD = 64;
+int launch_slogdet_batched(mln_ctx* ctx, const double* A, int64_t count, int k, int64_t lda, int lead, double* sign,
+                           double* logabs, int64_t inner, int64_t out_stride, int64_t out_off);
+
 // eigh.hip: symmetric eigensolver (block one-sided Jacobi); w_host ascending, Vrows row j = eigenvector j
 int dev_eigh(mln_ctx* ctx, const double* A, int64_t m, int64_t lda, double* w_host, double* Vrows, int64_t ldv,
              int* n_sweeps_out);
