@@ -168,14 +168,11 @@ int launch_kernel_grad(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t
 int launch_predict_gradient(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
                             int d, const double* w, double* out) {
   if (n == 0) return MLN_OK;
-  // single stationary leaf and enough pairs: covariance-tile pass + GEMM on the matrix cores (cov_kernels.hip)
-  if (cov.n_toks == 1 && cov.leaves[0].kind != MLN_K_LINEAR && n * m >= (int64_t)1 << 16)
-    return launch_predict_gradient_gemm(ctx, cov, x, n, c, m, d, w, out);
-  // composite program whose leaves are all stationary: the same idea with one coefficient matrix per leaf
+  // every leaf stationary and enough pairs: covariance-tile pass (one coefficient matrix per leaf) + GEMMs on the matrix
+  // cores (cov_predict_deriv.hip)
   bool stationary = cov.n_leaves >= 1;
   for (int l = 0; l < cov.n_leaves; ++l) stationary = stationary && cov.leaves[l].kind != MLN_K_LINEAR;
-  if (stationary && n * m >= (int64_t)1 << 16)
-    return launch_predict_gradient_gemm_multi(ctx, cov, x, n, c, m, d, w, out);
+  if (stationary && n * m >= (int64_t)1 << 16) return launch_predict_gradient_gemm(ctx, cov, x, n, c, m, d, w, out);
   const size_t lds = sizeof(double) * ((size_t)2 * d * GR + (size_t)GC * d + GC + (size_t)MLN_MAX_LEAVES * GC);
   if (lds > 160 * 1024) { mln_set_error(ctx, "predict_gradient: too many dimensions for the LDS layout"); return MLN_ERR_UNSUPPORTED; }
   MLN_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_predict_gradient),
@@ -183,46 +180,5 @@ int launch_predict_gradient(mln_ctx* ctx, const DevCov& cov, const double* x, in
   hipLaunchKernelGGL(k_predict_gradient, dim3((unsigned)((n + GR - 1) / GR)), dim3(GR), lds, ctx->stream, cov, x, n, c,
                      m, d, w, out);
   MLN_HIP(ctx, hipGetLastError());
-  return MLN_OK;
-}
-
-namespace {
-
-// dst[i * ldd + k] = src[i * lds + k], k < cols: column q of W into a vector, one output's (n x d) gradient into out[:, q, :]
-__global__ void k_copy_rows_strided(const double* __restrict__ src, int64_t lds, double* __restrict__ dst, int64_t ldd,
-                                    int64_t rows, int64_t cols) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= rows * cols) return;
-  const int64_t i = idx / cols, k = idx % cols;
-  dst[i * ldd + k] = src[i * lds + k];
-}
-
-}  // namespace
-
-// Gradient of a p-output predictive mean: out[i][q][:] = sum_j W[j][q] d cov(x_i, c_j) / d x_i   (out: n x p x d).
-//   p == 1                                   launch_predict_gradient itself
-//   stationary leaves only, n m >= 2^16      launch_predict_gradient_batched: the covariance epilogue once per pair
-//   anything else                            launch_predict_gradient per column (gathered weights, scattered result): the
-//                                            bits of the single-output call
-int launch_predict_gradient_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
-                                  int d, const double* W, int64_t p, double* out) {
-  if (n == 0 || p == 0) return MLN_OK;
-  if (p == 1) return launch_predict_gradient(ctx, cov, x, n, c, m, d, W, out);
-  bool stationary = cov.n_leaves >= 1;
-  for (int l = 0; l < cov.n_leaves; ++l) stationary = stationary && cov.leaves[l].kind != MLN_K_LINEAR;
-  if (stationary && n * m >= (int64_t)1 << 16) return launch_predict_gradient_batched(ctx, cov, x, n, c, m, d, W, p, out);
-  DevBuf<double> wq, gq;
-  if (m > 0) MLN_TRY(wq.alloc(ctx, (size_t)m, "wq"));
-  MLN_TRY(gq.alloc(ctx, (size_t)n * d, "gq"));
-  for (int64_t q = 0; q < p; ++q) {
-    if (m > 0)
-      hipLaunchKernelGGL(k_copy_rows_strided, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, W + q, p,
-                         wq.get(), (int64_t)1, m, (int64_t)1);
-    MLN_TRY(launch_predict_gradient(ctx, cov, x, n, c, m, d, wq.get(), gq.get()));
-    hipLaunchKernelGGL(k_copy_rows_strided, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const double*)gq.get(), (int64_t)d, out + q * d, p * d, n, (int64_t)d);
-  }
-  MLN_HIP(ctx, hipGetLastError());
-  MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MLN_OK;
 }

@@ -1,5 +1,5 @@
 // The per-leaf device arithmetic of the covariance kernels -- value, radial gradient factor g, second radial factor h and
-// the tiled leaf dot product -- shared by cov_kernels.hip, cov_grad.hip (one-program route) and cov_block_deriv.hip
+// the tiled leaf dot product -- shared by cov_kernels.hip, cov_predict_deriv.hip, cov_grad.hip (one-program routes) and cov_block_deriv.hip
 // (block-evaluated trees), so that every route evaluates a leaf with the same instructions.
 #pragma once
 #include "mln_internal.h"

@@ -1,4 +1,4 @@
-// Forward-mode differentiation of the postfix covariance program, shared by cov_grad.hip and cov_kernels.hip.
+// Forward-mode differentiation of the postfix covariance program, shared by cov_grad.hip and cov_predict_deriv.hip.
 #pragma once
 #include "mln_internal.h"
 

@@ -79,24 +79,20 @@ int launch_axpby(mln_ctx* ctx, int64_t n, double a, const double* x, double b, d
 // cov_grad.hip
 int launch_kernel_grad(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* y, int64_t m,
                        int d, int exact_denominator, double* out);
+int launch_predict_gradient(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
+                            int d, const double* w, double* out);              // out: n x d; picks the GEMM route or its own kernel
+
+// cov_predict_deriv.hip: gradient and Hessian of the predictive mean through coefficient matrices and GEMMs
 int launch_predict_gradient_gemm(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c,
-                                 int64_t m, int d, const double* w, double* out);   // single stationary leaf
-int launch_predict_gradient_gemm_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c,
-                                       int64_t m, int d, const double* w, double* out);   // stationary leaves, any program
+                                 int64_t m, int d, const double* w, double* out);   // stationary leaves, any program
 int launch_predict_hessian(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
                            int d, const double* w, double* out);              // out: n x d x d
-int launch_predict_gradient(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
-                            int d, const double* w, double* out);
-// p outputs, W m x p row-major, out n x p x d.  _batched (cov_kernels.hip): stationary leaves, one weight-less coefficient
-// pass per row chunk and GEMMs over blocks of outputs; _multi (cov_grad.hip) picks it, or launch_predict_gradient per column
-int launch_predict_gradient_batched(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c,
-                                    int64_t m, int d, const double* W, int64_t p, double* out);
+// p outputs, W m x p row-major, out n x p x d / n x p x d x d: p == 1 is the single-output launcher, few pairs (and for the
+// gradient a Linear leaf) go through it column by column, the rest through one weight-less coefficient pass per row chunk and
+// GEMMs over blocks of outputs.  _logdet: the same Hessians built in scratch and factored there -- only sign / logabs (n x p
+// each) are written.
 int launch_predict_gradient_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
                                   int d, const double* W, int64_t p, double* out);
-
-// Hessians of p outputs, W m x p row-major, out n x p x d x d (cov_kernels.hip): p == 1 and fewer than 2^16 pairs go through
-// launch_predict_hessian (per column), the rest through one weight-less coefficient pass per row chunk and GEMMs over blocks of
-// outputs.  _logdet: the same Hessians built in scratch and factored there -- only sign / logabs (n x p each) are written.
 int launch_predict_hessian_multi(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,
                                  int d, const double* W, int64_t p, double* out);
 int launch_predict_hessian_logdet(mln_ctx* ctx, const DevCov& cov, const double* x, int64_t n, const double* c, int64_t m,

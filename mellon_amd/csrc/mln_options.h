@@ -5,7 +5,7 @@
 //   MELLON_AMD_MIXED_MIN_ELEMS    n m below which the 32-bit copy is not made (default 2^27)        api_fit.hip
 //   MELLON_AMD_SURROGATE          float | fixed: format of the 32-bit copy                           api_fit.hip
 //   MELLON_AMD_NN_PREFILTER=0     exact 1-NN without the fp16-split pre-filter; _MIN: its pair count cov_kernels.hip
-//   MELLON_AMD_GRAD_COLS          GEMM columns per output block of the p-output gradient (512)      cov_kernels.hip
+//   MELLON_AMD_GRAD_COLS          GEMM columns per output block of the p-output gradient (512)      cov_predict_deriv.hip
 //   MELLON_AMD_NO_CACHE=1        no caching allocator                                               alloc.hip
 //   MELLON_AMD_RCCL               path of librccl                                                    comm.hip
 //   MELLON_AMD_TRACE, MELLON_AMD_TIMING=0     diagnostics: stage prints; no per-evaluation events    api_*.hip
