@@ -228,7 +228,23 @@ class DeviceArray:
         self.ctx._check(self.ctx.lib.mln_memcpy(self.ctx.handle, out.ctypes.data, self.ptr, self.nbytes))
         return out
 
+    def row(self, i):
+        """Row i of a 2-D array as a 1-D DeviceArray over the SAME memory (no copy; it keeps this array alive and frees
+        nothing): lets an operator that fills a vector write one row of a table in HBM."""
+        if self.ndim != 2 or not 0 <= int(i) < self.shape[0] or self.ptr is None:
+            raise ValueError(f"row({i}) of a DeviceArray of shape {self.shape}")
+        view = DeviceArray.__new__(DeviceArray)
+        view.ctx, view.shape, view.size = self.ctx, (self.shape[1],), self.shape[1]
+        view.ptr = self.ptr + 8 * int(i) * self.shape[1]
+        view._base = self
+        return view
+
+    _base = None      # the owning array of a view (row()): only the owner returns memory
+
     def free(self):
+        if self._base is not None:
+            self.ptr = self._base = None
+            return
         if self.ptr is not None and self.ctx.handle is not None:
             self.ctx.lib.mln_free(self.ctx.handle, self.ptr)
         self.ptr = None

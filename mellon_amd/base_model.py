@@ -123,8 +123,8 @@ class BaseEstimator:
         from .distributed import current
         if current().world_size > 1:
             raise NotImplementedError(
-                f"{what} need all cells; when cells are sharded across ranks pass `{what}=` explicitly "
-                "(replicated landmarks / ls_time, this rank's nn_distances).")
+                f"The {what} needs all cells on one rank and is not available when cells are sharded across "
+                "ranks; use a sparse gp_type (landmarks) there.")
 
     def _all_cells(self):
         """Cell-sharded fit: the cells of ALL ranks in rank order (host array, gathered once over the host

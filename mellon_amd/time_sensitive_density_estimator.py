@@ -83,21 +83,30 @@ class TimeSensitiveDensityEstimator(DensityEstimator):
 
     def _compute_ls_time(self):
         """time_sensitive_density_estimator.py:503-536: one density fit per time point, then the kernel length scale
-        that best explains the correlation of the densities across time."""
-        from .compute_ls_time import compute_ls_time
-        # The per-time-point fits run on whatever cells this rank holds: with sharded cells every rank would loop over
-        # its own set of time stamps (mismatched collectives) and correlate only local cells (a different ls_time, hence
-        # a different cov_func, per rank).  The device context's communicator is bound to all ranks, so a rank-0-only
-        # nested fit is not available either: the caller passes ls_time (a scalar, replicated) for sharded fits.
-        self._require_single_process("ls_time")
+        that best explains the correlation of the densities across time.
+
+        With cells sharded across ranks (compute_ls_time.compute_ls_time_sharded) every rank walks the global time
+        points, each time point is fitted on its cells of all ranks dealt out again in equal slices, and the
+        correlation comes from all-reduced sums: one `ls_time`, the same bits everywhere.  `_save_intermediate_ls_times`
+        then stores `densities` as this rank's T x n_local columns (every time point's density on this rank's cells),
+        `predictors` as the per-time-point estimators, whose predictors are replicated, and `numeric_stages` as the
+        global time stamps."""
+        from .compute_ls_time import compute_ls_time, compute_ls_time_sharded
+        from .distributed import current
         kwargs = {"cov_func_curry": self.cov_func_curry, "d_method": self.d_method, "d": self.d,
                   "optimizer": self.optimizer, "ls": self.ls, "ls_factor": self.ls_factor, "jit": self.jit,
                   "mu": self.mu}
         kwargs.update(self.density_estimator_kwargs)
         logger.info("Initiating density computation for each time point to estimate the 'ls_time' parameter. "
                     "You can directly specify 'ls_time' to bypass this computation-intensive step.")
-        ls = compute_ls_time(self.nn_distances, self.x, self.cov_func_curry,
-                             return_data=self._save_intermediate_ls_times, density_estimator_kwargs=kwargs)
+        comm = current()
+        if comm.world_size > 1:
+            ls = compute_ls_time_sharded(self.nn_distances, self.x, self.cov_func_curry, comm,
+                                         return_data=self._save_intermediate_ls_times,
+                                         density_estimator_kwargs=kwargs)
+        else:
+            ls = compute_ls_time(self.nn_distances, self.x, self.cov_func_curry,
+                                 return_data=self._save_intermediate_ls_times, density_estimator_kwargs=kwargs)
         if self._save_intermediate_ls_times:
             logger.info("Storing `self.densities`, `self.predictors`, and `self.numeric_stages`.")
             ls, self.densities, self.predictors, self.numeric_stages = ls
