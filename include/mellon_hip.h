@@ -483,6 +483,20 @@ int mln_sparse_solve_noise(mln_ctx* ctx, const mln_kernel_desc* cov, const doubl
                            int32_t d, const double* xu, int64_t m, const double* y, int64_t p, double mu,
                            const double* sigma, int32_t sigma_kind, double jitter, double* W /* m x p */);
 
+/* The same solve for 2-D targets given in CSR (an AnnData `.X`): y (n_local x p) is indptr[n_local + 1], indices[nnz],
+ * data[nnz] with nnz = indptr[n_local] -- HOST arrays (a device pointer is MLN_ERR_ARG).  sigma_kind is MLN_SIGMA_SCALAR
+ * (sigma[1]; Lp_out / Cs_out as in mln_sparse_solve_factors, either may be NULL) or MLN_SIGMA_PER_OUTPUT (sigma[p], no
+ * factors); MLN_SIGMA_PER_CELL is MLN_ERR_ARG (that model takes a 1-D y).
+ * Before anything is launched one host pass checks indptr[0] == 0, indptr non-decreasing, per row the indices strictly
+ * increasing and inside [0, p), the data finite: a violation is MLN_ERR_ARG with a message naming the row.
+ * No n x p array is formed: y - mu exists one row panel at a time (a byte budget: rows = budget / 8p, a multiple of 64, at
+ * least 64), built in HBM from the CSR arrays and fed to the GEMM that forms A (y - mu); the panels accumulate in a fixed
+ * order, so two calls return the same bits.  Everything after that product is the code of the dense entries.            */
+int mln_sparse_solve_csr(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, int64_t n_local, int32_t d,
+                         const double* xu, int64_t m, const int64_t* indptr, const int32_t* indices,
+                         const double* data, int64_t p, double mu, const double* sigma, int32_t sigma_kind,
+                         double jitter, double* W /* m x p */, double* Lp_out, double* Cs_out);
+
 /* Full GP conditioned on p outputs with one noise level each (conditional.py:239-251; leverage :313-323,385-403;
  * HC3 residuals :330-333; variance weights :338-350) from ONE eigendecomposition K = U diag(lam) U^T of the n x n
  * kernel matrix: (K + (sigma_j^2 + jitter) I)^-1 = U diag(1 / (lam + sigma_j^2 + jitter)) U^T.

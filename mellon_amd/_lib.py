@@ -16,6 +16,13 @@ LIB_PATH = os.path.join(_HERE, "libmellon_hip.so")
 MLN_OK, MLN_ERR_NOT_PD, MLN_ERR_SHAPE, MLN_ERR_HIP, MLN_ERR_RCCL, MLN_ERR_ARG, MLN_ERR_UNSUPPORTED = range(7)
 MLN_UNIQUE_ID_BYTES = 128
 MLN_N_STAGE_TIMES = 26
+CSR_PANEL_BYTES = 64 << 20      # csrc/sparse_targets.hip: bytes of one row panel of y - mu built from CSR targets
+
+
+def csr_panel_rows(p):
+    """Rows of y - mu that mln_sparse_solve_csr holds in HBM at a time: the byte budget over 8 p, a multiple of 64, >= 64."""
+    rows = CSR_PANEL_BYTES // (8 * int(p))
+    return max(64, rows - rows % 64)
 
 K_MATERN32, K_MATERN52, K_EXPQUAD, K_EXPONENTIAL, K_RATQUAD, K_LINEAR, K_DISTANCE = 1, 2, 3, 4, 5, 6, 7
 OP_LEAF, OP_CONST, OP_ADD, OP_MUL, OP_POW = 0, 1, 2, 3, 4
@@ -140,6 +147,8 @@ SYMBOLS = [
     ("mln_sparse_solve_factors", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dbl, _dbl, _dbl, _dp,
                                            _dp, _dp]),
     ("mln_sparse_solve_noise", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dbl, _dp, _i32, _dbl, _dp]),
+    ("mln_sparse_solve_csr", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _vp, _vp, _dp, _i64, _dbl, _dp, _i32, _dbl, _dp,
+                                       _dp, _dp]),
     ("mln_full_conditional_noise", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dbl, _dp, _dbl, _dp, _dp, _dp, _dp]),
     ("mln_landmark_leverage", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _dp, _i64, _dbl, _dp]),
     ("mln_predict_mean", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dbl, _dp]),
@@ -743,6 +752,39 @@ class Context:
 
     SIGMA_SCALAR, SIGMA_PER_OUTPUT, SIGMA_PER_CELL = 0, 1, 2
 
+    def sparse_solve_csr(self, desc, x, xu, y, mu, sigma, kind, jitter, return_factors=False):
+        """Weights of the noisy landmark conditional for 2-D targets held in CSR (`y`: anything with `indptr`, `indices`,
+        `data`, `shape`, e.g. validation.CSRTargets): y - mu only ever exists as one row panel in HBM
+        (mln_sparse_solve_csr).  kind: SIGMA_SCALAR (with return_factors also Lp and Cs = Lp L_B) or SIGMA_PER_OUTPUT."""
+        n, p = (int(s) for s in y.shape)
+        if isinstance(desc, BlockEvaluatedCov):
+            sig = _f64(np.atleast_1d(sigma))
+            W, Lp, Cs = self._sparse_solve_blocks(desc, x, xu, y, mu, sig, jitter, return_factors)
+            return (W, Lp, Cs) if return_factors else W
+        x = x if isinstance(x, DeviceArray) else _as2d(x)
+        xu = _as2d(xu)
+        indptr = np.ascontiguousarray(y.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(y.indices, dtype=np.int32)
+        data = _f64(y.data)
+        sig = _f64(np.atleast_1d(sigma))
+        # the array lengths are known here only (the C entry reads nnz from indptr[n]): refused like its own findings
+        if x.shape[0] != n or indptr.shape != (n + 1,) or indices.ndim != 1 or indices.shape != data.shape \
+                or int(indptr[-1]) != data.shape[0]:
+            raise MellonHipError(f"libmellon_hip error {MLN_ERR_ARG}: CSR targets: indptr must hold n + 1 = {n + 1} offsets "
+                                 f"ending at nnz = {data.shape[0]} (got {indptr.shape[0]} ending at "
+                                 f"{int(indptr[-1]) if indptr.size else None})")
+        want = {self.SIGMA_SCALAR: 1, self.SIGMA_PER_OUTPUT: p}.get(int(kind))
+        if want is not None and sig.shape != (want,):
+            raise ValueError(f"sigma has shape {sig.shape}, expected {(want,)} for noise kind {kind}")
+        m = xu.shape[0]
+        W = np.empty((m, p), dtype=np.float64)
+        Lp, Cs = (np.empty((m, m)), np.empty((m, m))) if return_factors else (None, None)
+        self._check(self.lib.mln_sparse_solve_csr(self.handle, desc.ref, _ptr(x), n, x.shape[1], _ptr(xu), m,
+                                                  indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, p,
+                                                  float(mu), sig.ctypes.data, int(kind), float(jitter), W.ctypes.data,
+                                                  _ptr(Lp), _ptr(Cs)), jitter=jitter)
+        return (W, Lp, Cs) if return_factors else W
+
     def _sparse_solve_blocks(self, desc, x, xu, y, mu, sigma, jitter, return_factors):
         """The landmark conditional (conditional.py:57-66,526-545) of a block-evaluated covariance, assembled from the
         library's device primitives: G = K^T K and R = K^T (y - mu) accumulate over row blocks on the matrix cores
@@ -751,10 +793,17 @@ class Context:
         mln_trsm_lower.  sigma: one value, or one per output column (columns that share a value share the factor)."""
         xh = x.to_host() if isinstance(x, DeviceArray) else _as2d(x)
         xu = _as2d(xu)
-        yh = y.to_host() if isinstance(y, DeviceArray) else _f64(y)
-        y_ndim = yh.ndim
-        r = (yh - float(mu)).reshape(xh.shape[0], -1)
-        m, p = xu.shape[0], r.shape[1]
+        if hasattr(y, "indptr") and hasattr(y, "rows"):
+            # CSR targets (validation.CSRTargets): r is formed per row block from the holder, never as a whole
+            y_ndim, p = 2, int(y.shape[1])
+            r_block = lambda i0, i1: y.rows(i0, i1) - float(mu)
+        else:
+            yh = y.to_host() if isinstance(y, DeviceArray) else _f64(y)
+            y_ndim = yh.ndim
+            r = (yh - float(mu)).reshape(xh.shape[0], -1)
+            p = r.shape[1]
+            r_block = lambda i0, i1: np.ascontiguousarray(r[i0:i1])
+        m = xu.shape[0]
         if sigma.shape[0] not in (1, p):
             raise ValueError(f"sigma has shape {sigma.shape}, expected (1,) or ({p},)")
         G, R = self.to_device(np.zeros((m, m))), self.to_device(np.zeros((m, p)))
@@ -762,7 +811,7 @@ class Context:
             blk = desc.block(xh[i0:i0 + desc.rows_per_block], xu)
             blk = blk if isinstance(blk, DeviceArray) else self.to_device(blk)
             self.gemm(blk, blk, ta=True, out=G, beta=1.0)
-            self.gemm(blk, np.ascontiguousarray(r[i0:i0 + desc.rows_per_block]), ta=True, out=R, beta=1.0)
+            self.gemm(blk, r_block(i0, i0 + desc.rows_per_block), ta=True, out=R, beta=1.0)
         G, R = self.allreduce_sum(G).to_host(), self.allreduce_sum(R).to_host()
         Kuu = desc.block(xu, xu)
         Kuu = Kuu.to_host() if isinstance(Kuu, DeviceArray) else Kuu

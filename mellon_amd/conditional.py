@@ -15,6 +15,7 @@ from . import _lib
 from .base_predictor import ExpPredictor, Predictor, PredictorTime
 from .decomposition import FactorL, FactorLp
 from .util import DEFAULT_JITTER, ensure_2d
+from .validation import CSRTargets
 
 DEFAULT_SIGMA = 0
 SPECTRAL_MIN_LEVELS = 8      # distinct noise levels above which the landmark leverage goes spectral
@@ -34,7 +35,7 @@ def _is_per_feature_sigma(sigma, y):
     """One sigma per output column of a 2-D y -- shapes (p,), (1, p), (n, p) (conditional.py:13-36)."""
     if sigma is None or np.ndim(sigma) == 0:
         return False
-    sigma, y = np.asarray(sigma), np.asarray(y)
+    sigma, y = np.asarray(sigma), (y if isinstance(y, CSRTargets) else np.asarray(y))      # (only y's shape is read)
     if sigma.ndim == 2 and sigma.shape[0] == 1 and y.ndim == 2 and sigma.shape[1] == y.shape[1]:
         return True
     if sigma.ndim == 2 and y.ndim == 2 and sigma.shape == y.shape:
@@ -62,6 +63,14 @@ def _per_output_levels(sigma):
                                   "per column).")
     levels, inverse = np.unique(sig, return_inverse=True)
     return sig, [(float(v), np.flatnonzero(inverse == k)) for k, v in enumerate(levels)]
+
+
+def _densified(y, why):
+    """Sparse targets as one dense array, for the routes whose operands or outputs are n x p anyway."""
+    if isinstance(y, CSRTargets):
+        logger.info("The sparse targets are made dense once (%s).", why)
+        return y.toarray()
+    return y
 
 
 def _hc3(residual, h):
@@ -221,7 +230,7 @@ class _FullConditional:
                  y_is_mean=False, with_uncertainty=False, obs_variance=False, parameter_std=None, factor=None):
         x = np.ascontiguousarray(ensure_2d(x), dtype=np.float64)
         ctx = _lib.default_context()
-        yh = np.asarray(y, dtype=np.float64)
+        yh = np.asarray(_densified(y, "the weights of the full GP are n x p"), dtype=np.float64)
         n = x.shape[0]
         per_feature = _is_per_feature_sigma(sigma, yh)
         per_cell = (not per_feature and sigma is not None and np.ndim(sigma) == 1 and L is None and not y_is_mean)
@@ -368,7 +377,17 @@ class _LandmarksConditional:
         xh = x if isinstance(x, _lib.DeviceArray) else np.ascontiguousarray(ensure_2d(x), dtype=np.float64)
         xu = np.ascontiguousarray(ensure_2d(xu), dtype=np.float64)
         y_resident = isinstance(y, _lib.DeviceArray)              # targets already in HBM: scalar-sigma solve only
-        yh = y if y_resident else np.asarray(y, dtype=np.float64)
+        if isinstance(y, CSRTargets):
+            # CSR targets stay sparse for one sigma and one sigma per output column (mln_sparse_solve_csr).  The other
+            # routes have n x p operands or outputs of their own and take the targets dense.
+            if y_is_mean or y_cov_factor is not None:
+                y = _densified(y, "y_is_mean / y_cov_factor work on n x p factors")
+            elif obs_variance:
+                y = _densified(y, "obs_variance forms the n x p residuals")
+            elif sigma is not None and np.ndim(sigma) >= 1 and np.shape(sigma) not in ((y.shape[1],), (1, y.shape[1])):
+                y = _densified(y, "this sigma is element-wise")
+        y_sparse = isinstance(y, CSRTargets)
+        yh = y if (y_resident or y_sparse) else np.asarray(y, dtype=np.float64)
         desc = cov_func.lower(xu.shape[1])
         per_feature = False if y_resident else _is_per_feature_sigma(sigma, yh)
         vector = (not per_feature) and (not y_is_mean) and sigma is not None and np.ndim(sigma) >= 1
@@ -378,6 +397,12 @@ class _LandmarksConditional:
 
         def solve(target, mean, want_factors=False):
             """`_sparse_solve` of `target - mean` under this conditional's noise model."""
+            if isinstance(target, CSRTargets):
+                if per_feature:
+                    return ctx.sparse_solve_csr(desc, xh, xu, target, mean, _normalize_per_feature_sigma(sigma),
+                                                ctx.SIGMA_PER_OUTPUT, jitter)
+                return ctx.sparse_solve_csr(desc, xh, xu, target, mean, s, ctx.SIGMA_SCALAR, jitter,
+                                            return_factors=want_factors)
             if per_feature:
                 return _sparse_solve_per_output(ctx, desc, xh, xu, target, mean, sigma, jitter)
             if vector:
@@ -469,7 +494,7 @@ class _LandmarksConditionalCholesky:
                                  "(the reference divides by sigma^2, conditional.py:157-159).")
             ctx = _lib.default_context()
             ox = np.ascontiguousarray(ensure_2d(obs_x), dtype=np.float64)
-            oy = np.asarray(obs_y, dtype=np.float64)
+            oy = np.asarray(_densified(obs_y, "obs_variance forms the n x p residuals"), dtype=np.float64)
             h = self._leverage(ox, s)          # before `L` is attached: K_uu = cov(xu, xu), as in the reference
             self._corrected_r2 = _hc3(oy - self._mean(ox), h)
             self.variance_mu = 0.0

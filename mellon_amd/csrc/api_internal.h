@@ -213,8 +213,14 @@ int fit_precond_revert(mln_fit* f);
 int fit_small_gemv(mln_fit* f, const double* M, int trans, const double* w, double* y);
 int launch_scale_rows_cols(mln_ctx* ctx, double* A, int64_t ld, int64_t rows, int64_t cols, const double* row,
                                   const double* col);
+// sparse_targets.hip: 2-D targets kept in CSR (host arrays the entry has validated; nnz = indptr[n]).
+struct CsrTargets { const int64_t* indptr; const int32_t* indices; const double* data; int64_t nnz; };
+// C (m x p, ldc = p) = alpha * L^T (y - mu), L = n x m with pitch ldl, from row panels of y - mu built in HBM
+int csr_targets_product(mln_ctx* ctx, const double* L, int64_t ldl, int64_t m, int64_t n, int64_t p,
+                        const CsrTargets& y, double mu, double alpha, double* C);
+// y: dense n_local x p, or NULL with `csr` set
 int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, int64_t n_local,
                              int32_t d, const double* xu, int64_t m, const double* y, int64_t p, double mu,
                              const double* sigmas, int32_t kind, double jitter, double* W, double* Lp_out,
-                             double* Cs_out);
+                             double* Cs_out, const CsrTargets* csr = nullptr);
 unsigned grid_1d(int64_t count);

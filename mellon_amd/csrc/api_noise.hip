@@ -44,8 +44,8 @@ static constexpr int SPECTRAL_MIN_LEVELS = 32;   // runs of equal sigma above wh
 int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x, int64_t n_local,
                              int32_t d, const double* xu, int64_t m, const double* y, int64_t p, double mu,
                              const double* sigmas, int32_t kind, double jitter, double* W, double* Lp_out,
-                             double* Cs_out) {
-  if (!ctx || !xu || !W || !sigmas || (n_local > 0 && (!x || !y))) return MLN_ERR_ARG;
+                             double* Cs_out, const CsrTargets* csr) {
+  if (!ctx || !xu || !W || !sigmas || (n_local > 0 && (!x || (!y && !csr)))) return MLN_ERR_ARG;
   if (p < 1 || m < 1) { mln_set_error(ctx, "bad shape"); return MLN_ERR_SHAPE; }
   if (kind < MLN_SIGMA_SCALAR || kind > MLN_SIGMA_PER_CELL) { mln_set_error(ctx, "unknown sigma kind"); return MLN_ERR_ARG; }
   if (kind != MLN_SIGMA_SCALAR && (Lp_out || Cs_out)) {
@@ -84,9 +84,9 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
   if (rc == MLN_OK && n_groups > 1) rc = G0.alloc(ctx, (size_t)m * ldg, "G0");
   if (rc == MLN_OK) rc = C.alloc(ctx, (size_t)m * p, "C");
   DevIn dy;
-  if (rc == MLN_OK) rc = dy.init(ctx, y, (size_t)n * p);
-  // r = y - mu
-  if (rc == MLN_OK && n > 0) {
+  if (rc == MLN_OK && !csr) rc = dy.init(ctx, y, (size_t)n * p);
+  // r = y - mu  (CSR targets: formed panel by panel where C is, sparse_targets.hip)
+  if (rc == MLN_OK && n > 0 && !csr) {
     rc = R.alloc(ctx, (size_t)n * p, "R");
     chk(hipMemcpyAsync(R, dy.dev, sizeof(double) * (size_t)n * p, hipMemcpyDeviceToDevice, ctx->stream));
     if (rc == MLN_OK && mu != 0.0) {
@@ -112,18 +112,24 @@ int sparse_solve_impl(mln_ctx* ctx, const mln_kernel_desc* cov, const double* x,
   if (rc == MLN_OK) rc = fit_gram(f, n_groups > 1 ? G0 : G, ldg, 1);
   // C = A r = L^T r   (m x p), split over cells; the 1 / sigma^2 is applied per group below
   if (rc == MLN_OK) {
-    int split = (int)(n / 8192);
-    if (split < 1) split = 1;
-    if (split > 16) split = 16;
     const size_t stride = (size_t)m * p;
-    if (split > 1) rc = parts.alloc(ctx, stride * split, "parts");
-    if (rc == MLN_OK) chk(hipMemsetAsync(split > 1 ? parts : C, 0, sizeof(double) * stride * (split > 1 ? split : 1), ctx->stream));
-    GemmArgs g{};
-    g.A = f->L; g.lda = f->ldl; g.B = R; g.ldb = p; g.C = (split > 1) ? parts : C; g.ldc = p;
-    g.M = m; g.N = p; g.K = n; g.alpha = (n_groups == 1) ? 1.0 / g_s2[0] : 1.0; g.beta = 0.0; g.ta = 1; g.tb = 0;
-    g.split_k = split; g.c_split_stride = (int64_t)stride;
-    if (rc == MLN_OK && n > 0) rc = launch_dgemm(ctx, g);
-    if (rc == MLN_OK && split > 1) rc = launch_sum_partials(ctx, parts, split, (int64_t)stride, C, (int64_t)stride, 0.0);
+    const double alpha = (n_groups == 1) ? 1.0 / g_s2[0] : 1.0;
+    if (csr) {
+      // CSR targets: row panels of y - mu are built in HBM and fed to the same GEMM (sparse_targets.hip)
+      rc = csr_targets_product(ctx, f->L, f->ldl, m, n, p, *csr, mu, alpha, C);
+    } else {
+      int split = (int)(n / 8192);
+      if (split < 1) split = 1;
+      if (split > 16) split = 16;
+      if (split > 1) rc = parts.alloc(ctx, stride * split, "parts");
+      if (rc == MLN_OK) chk(hipMemsetAsync(split > 1 ? parts : C, 0, sizeof(double) * stride * (split > 1 ? split : 1), ctx->stream));
+      GemmArgs g{};
+      g.A = f->L; g.lda = f->ldl; g.B = R; g.ldb = p; g.C = (split > 1) ? parts : C; g.ldc = p;
+      g.M = m; g.N = p; g.K = n; g.alpha = alpha; g.beta = 0.0; g.ta = 1; g.tb = 0;
+      g.split_k = split; g.c_split_stride = (int64_t)stride;
+      if (rc == MLN_OK && n > 0) rc = launch_dgemm(ctx, g);
+      if (rc == MLN_OK && split > 1) rc = launch_sum_partials(ctx, parts, split, (int64_t)stride, C, (int64_t)stride, 0.0);
+    }
     if (rc == MLN_OK) rc = dev_allreduce(ctx, C, (int64_t)stride);
     if (rc == MLN_OK && n_groups > 1) {
       std::vector<double> inv((size_t)p);

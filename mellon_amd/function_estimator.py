@@ -8,7 +8,8 @@ from .base_model import BaseEstimator, DEFAULT_COV_FUNC
 from .inference import DEFAULT_INIT_LEARN_RATE, DEFAULT_N_ITER, DEFAULT_OPTIMIZER, compute_conditional
 from .parameters import DEFAULT_RANDOM_SEED
 from .util import DEFAULT_JITTER, GaussianProcessType
-from .validation import validate_array, validate_bool, validate_float, validate_float_or_iterable_numerical
+from .validation import (CSRTargets, validate_array, validate_bool, validate_float, validate_float_or_iterable_numerical,
+                         validate_targets)
 
 logger = logging.getLogger("mellon")
 
@@ -67,19 +68,27 @@ class FunctionEstimator(BaseEstimator):
         if y is None:
             raise ValueError("Required argument y is missing.")
         obs_variance = self.obs_variance if obs_variance is None else obs_variance
+        if not isinstance(y, CSRTargets):
+            y = validate_targets(y, "y")            # a 2-D sparse y stays sparse (CSR) down to the device
         self.conditional = compute_conditional(
             x, self.landmarks, None, None, y, self.mu, self.cov_func, None, None, self.sigma, jitter=self.jitter,
             y_is_mean=self.y_is_mean, with_uncertainty=self.predictor_with_uncertainty, obs_variance=obs_variance)
         return self.conditional
 
     def fit(self, x=None, y=None, obs_variance=None):
+        return self._fit_targets(x, y, obs_variance)
+
+    def _fit_targets(self, x, y, obs_variance=None, functions_in_rows=False):
+        """fit(); with functions_in_rows `y` holds one function per ROW (multi_fit_predict) and is transposed by the
+        validator -- a sparse one without a dense detour."""
         x = self.set_x(x)
-        y = validate_array(y, "y")
-        if y.shape[0] != x.shape[0]:
-            raise ValueError(f"X.shape[0] = {x.shape[0]:,} (n_samples) should equal y.shape[0] = {y.shape[0]:,}.")
+        targets = validate_targets(y, "Y" if functions_in_rows else "y", transpose=functions_in_rows)
+        if targets.shape[0] != x.shape[0]:
+            raise ValueError(f"X.shape[0] = {x.shape[0]:,} (n_samples) should equal y.shape[0] = {targets.shape[0]:,}.")
         self.prepare_inference(x)
-        self.compute_conditional(x, y, obs_variance=obs_variance)
-        self.y = y
+        self.compute_conditional(x, targets, obs_variance=obs_variance)
+        # the validated array as before; of a sparse y the caller's own object (its transpose for functions in rows)
+        self.y = (y.T if functions_in_rows else y) if isinstance(targets, CSRTargets) else targets
         return self
 
     @property
@@ -114,5 +123,5 @@ class FunctionEstimator(BaseEstimator):
 
     def multi_fit_predict(self, x=None, Y=None, Xnew=None):
         """Functions stored as ROWS of Y (reference function_estimator.py multi_fit_predict)."""
-        Y = validate_array(Y, "Y")
-        return self.fit_predict(x, Y.T, Xnew).T
+        self._fit_targets(x, Y, functions_in_rows=True)
+        return self.predict(self.x if Xnew is None else validate_array(Xnew, "Xnew")).T

@@ -7,6 +7,84 @@ import numpy as np
 logger = logging.getLogger("mellon")
 
 
+def _is_sparse(a):
+    """A sparse container, by its methods (SciPy's *_matrix / *_array and anything shaped like them)."""
+    return hasattr(a, "todense") or (hasattr(a, "toarray") and hasattr(a, "tocsr"))
+
+
+class CSRTargets:
+    """2-D targets (n x p) kept sparse on the host, in the layout mln_sparse_solve_csr reads: `indptr` int64 (n + 1),
+    `indices` int32 (nnz), `data` float64 (nnz).  Canonical: per row the indices strictly increase (sorted, duplicates
+    summed); stored zeros stay stored values."""
+    ndim = 2
+
+    def __init__(self, indptr, indices, data, shape):
+        self.indptr, self.indices, self.data = indptr, indices, data
+        self.shape = (int(shape[0]), int(shape[1]))
+
+    @property
+    def nnz(self):
+        return int(self.data.shape[0])
+
+    def rows(self, i0, i1):
+        """Rows [i0, i1) as a dense float64 block."""
+        i0, i1 = max(0, int(i0)), min(self.shape[0], int(i1))
+        out = np.zeros((max(i1 - i0, 0), self.shape[1]), dtype=np.float64)
+        if i1 > i0:
+            q0, q1 = int(self.indptr[i0]), int(self.indptr[i1])
+            r = np.repeat(np.arange(i1 - i0), np.diff(self.indptr[i0:i1 + 1]))
+            out[r, self.indices[q0:q1]] = self.data[q0:q1]
+        return out
+
+    def toarray(self):
+        return self.rows(0, self.shape[0])
+
+
+def csr_targets(sparse, name, transpose=False):
+    """The canonical CSRTargets of a 2-D sparse container (of its transpose with `transpose`: the rows-are-functions layout
+    of multi_fit_predict), through the container's own `tocsr()`; no dense array is formed."""
+    c = (sparse.T if transpose else sparse).tocsr()
+    n, p = (int(s) for s in c.shape)
+    if p >= 2 ** 31:
+        raise ValueError(f"'{name}' has {p:,} columns; sparse targets take fewer than 2^31.")
+    try:
+        data = np.ascontiguousarray(c.data, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError(f"'{name}' should be numeric, got sparse data of dtype {getattr(c.data, 'dtype', None)} instead.")
+    indptr = np.ascontiguousarray(c.indptr, dtype=np.int64)
+    cols = np.asarray(c.indices, dtype=np.int64)
+    if indptr.shape != (n + 1,) or indptr[0] != 0 or indptr[-1] != data.shape[0] or cols.shape != data.shape \
+            or np.any(np.diff(indptr) < 0) or (cols.size and (cols.min() < 0 or cols.max() >= p)):
+        raise ValueError(f"'{name}' is not a valid CSR matrix (indptr / indices do not describe its shape {(n, p)}).")
+    if not np.all(np.isfinite(data)):
+        raise ValueError(f"'{name}' holds non-finite values.")
+    # canonical form: position = row * p + column strictly increasing; otherwise sort and sum what shares a position
+    key = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr)) * p + cols
+    if key.size > 1 and not np.all(key[1:] > key[:-1]):
+        order = np.argsort(key, kind="stable")
+        key, data = key[order], data[order]
+        first = np.flatnonzero(np.concatenate(([True], key[1:] != key[:-1])))
+        key, data = key[first], np.add.reduceat(data, first)
+        cols = key % p
+        indptr = np.concatenate(([0], np.cumsum(np.bincount(key // p, minlength=n)))).astype(np.int64)
+    # (float64 data in canonical order is used in place: the holder is read-only and lives for one fit)
+    return CSRTargets(indptr, np.ascontiguousarray(cols, dtype=np.int32), np.ascontiguousarray(data), (n, p))
+
+
+def validate_targets(y, name, transpose=False):
+    """The targets of a FunctionEstimator fit: a 2-D sparse container stays sparse (CSRTargets), everything else is
+    validate_array's dense float64 array (transposed with `transpose`)."""
+    if y is not None and _is_sparse(y) and hasattr(y, "tocsr") and len(getattr(y, "shape", ())) == 2:
+        return csr_targets(y, name, transpose=transpose)
+    y = validate_array(y, name)
+    return y.T if transpose else y
+
+
+def dense_targets(y):
+    """A dense float64 array of the targets, whatever validate_targets returned."""
+    return y.toarray() if isinstance(y, CSRTargets) else y
+
+
 def validate_array(iterable, name, optional=False, ndim=None):
     """reference validation.py:302-361."""
     if iterable is None:
@@ -18,6 +96,10 @@ def validate_array(iterable, name, optional=False, ndim=None):
         return iterable
     if isinstance(iterable, np.ndarray) and iterable.dtype == np.float64:
         array = iterable      # identity is preserved on purpose (set_x compares with `is`)
+    elif _is_sparse(iterable):
+        # reference validation.py:344-345: anything with `todense` is densified (recognised by its methods: no SciPy import)
+        dense = iterable.toarray() if hasattr(iterable, "toarray") else iterable.todense()
+        array = np.ascontiguousarray(np.asarray(dense), dtype=np.float64)
     else:
         try:
             array = np.asarray(iterable, dtype=np.float64)
