@@ -402,7 +402,9 @@ def test_kmeans_landmarks(ctx):
 
 @pytest.mark.parametrize("m", [2100, 6000, 8100])
 def test_objective_wide_landmark_counts(ctx, m):
-    """Every column-per-thread specialisation of k_objective (m up to the 8192 limit) against NumPy."""
+    """Three arms of k_objective's dispatch against NumPy, with the preconditioned objective on top: 3, 6 and 8 column
+    pairs per thread (<3,4,VEC>, <6,2>, <8,1>).  Every arm, mode and row map, at the edges of each, is in
+    tests/test_gpu_objective.py."""
     from mellon_amd import _lib
     rng = np.random.default_rng(m)
     n = 1500
