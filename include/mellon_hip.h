@@ -580,6 +580,18 @@ int mln_predict_mean_covariance(mln_ctx* ctx, const mln_kernel_desc* cov, const 
                                 int32_t d, const double* centers, int64_t m, const double* W, int64_t q,
                                 int32_t diag, double* out);
 
+/* Both variances for n queries at T times in one call, for cov((x,t),(c,s)) = k_state(x,c) k_time(t,s).
+ * state: the state factor's program over all d columns; S (T x m) = k_time(t, s_j), kdiag (T) = k_time(t, t), from the
+ * caller.  cov_out / mcov_out: n x T row-major, either may be NULL (not both):
+ *   cov [i,t] = kss_i kdiag_t - |K_t Lf^-T|^2  (+ |K_t Cs^-T|^2 with Cs, as the noisy landmark conditional adds it)
+ *   mcov[i,t] = |K_t W|^2 for W (m x q), or sum_q w_std_q^2 (K_t Lf^-T)_q^2 for w_std (m) -- W = Lf^-T diag(w_std) without a
+ *   second product; W and w_std exclude each other.
+ * scratch_doubles: the budget of the row-chunk and time-block buffers (0: 2^27); never fewer than 64 rows or one time. */
+int mln_predict_variance_grid(mln_ctx* ctx, const mln_kernel_desc* state, const double* xq, int64_t n, int32_t d,
+                              const double* centers, int64_t m, const double* S, int64_t T, const double* kdiag,
+                              const double* Lf, const double* Cs, const double* W, int64_t q, const double* w_std,
+                              int64_t scratch_doubles, double* cov_out, double* mcov_out);
+
 /* wall-clock seconds of the stages of the last mln_fit_prepare / mln_ridge_init and counters
  * of mln_objective: [0] kernel matrix, [1] cholesky, [2] trsm, [3] ridge gram, [4] ridge solve,
  * [5] objective kernel time (sum, HIP events), [6] objective launches, [7] bytes of L streamed

@@ -154,6 +154,8 @@ SYMBOLS = [
     ("mln_predict_mean", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dbl, _dp]),
     ("mln_predict_covariance", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i32, _dp]),
     ("mln_predict_mean_covariance", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _i32, _dp]),
+    ("mln_predict_variance_grid", C.c_int, [_vp, _KD, _dp, _i64, _i32, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _dp, _i64, _dp,
+                                            _i64, _dp, _dp]),
     ("mln_stage_times", C.c_int, [_vp, _dp]),
     ("mln_diag_peak", C.c_int, [_vp, _i32, _i64, C.POINTER(_dbl)]),
     ("mln_diag_overlap", C.c_int, [_vp, _i64, _i64, _i32, _i64, _dp]),
@@ -725,6 +727,37 @@ class Context:
                                                          _ptr(centers), centers.shape[0], _ptr(W), W.shape[1],
                                                          1 if diag else 0, out.ctypes.data))
         return out
+
+    def predict_variance_grid(self, state_desc, Xq, centers, S, kdiag, Lf, Cs=None, W=None, std=None,
+                              want=("cov", "mcov"), scratch_doubles=0):
+        """Variances of a separable time-sensitive covariance at every (query, time) pair in one device call
+        (mln_predict_variance_grid).  state_desc: the state factor over all columns of Xq (n, d); S (T, m) and kdiag (T,):
+        the time factor against the centres' times and on its own diagonal.  want: "cov" (k - |K L^-T|^2, plus the `Cs`
+        term when given) and / or "mcov" (|K W|^2 for W (m, q), or sum std^2 (K L^-T)^2 for std (m,) -- the W = L^-T
+        diag(std) of the Laplace / ADVI predictors without a second product).  Returns the (n, T) arrays in the order of
+        `want` (one array for a single name)."""
+        _needs_program(state_desc, "predict_variance_grid")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(w not in ("cov", "mcov") for w in want):
+            raise ValueError(f"want={want!r}: names are 'cov' and 'mcov'")
+        Xq, centers, S = _as2d(Xq), _as2d(centers), _as2d(S)
+        (n, d), m, T = Xq.shape, centers.shape[0], S.shape[0]
+        kdiag = _f64(kdiag).reshape(-1)
+        if S.shape[1] != m or kdiag.shape[0] != T or centers.shape[1] != d:
+            raise ValueError(f"S {S.shape} / kdiag {kdiag.shape} do not go with {m} centres and {T} times")
+        Lf, Cs, std = (None if a is None else _f64(a) for a in (Lf, Cs, std))
+        W = None if W is None else _as2d(W)
+        for name, a, shape in (("Lf", Lf, (m, m)), ("Cs", Cs, (m, m)), ("std", std, (m,))):
+            if a is not None and a.shape != shape:
+                raise ValueError(f"{name} of shape {a.shape}: expected {shape}")
+        if W is not None and W.shape[0] != m:
+            raise ValueError(f"W of shape {W.shape} does not go with {m} centres")
+        outs = {w: np.empty((n, T), dtype=np.float64) for w in want}
+        self._check(self.lib.mln_predict_variance_grid(
+            self.handle, state_desc.ref, _ptr(Xq), n, d, _ptr(centers), m, _ptr(S), T, _ptr(kdiag), _ptr(Lf), _ptr(Cs),
+            _ptr(W), 0 if W is None else W.shape[1], _ptr(std), int(scratch_doubles), _ptr(outs.get("cov")),
+            _ptr(outs.get("mcov"))))
+        return outs[want[0]] if len(want) == 1 else tuple(outs[w] for w in want)
 
     def sparse_solve(self, desc, x, xu, y, mu, sigma, jitter, return_factors=False):
         """Weights of the noisy landmark conditional; with return_factors also (Lp, Cs = Lp L_B)."""

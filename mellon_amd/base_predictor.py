@@ -359,8 +359,8 @@ class PredictorTime(Predictor):
     # -- one multi-output prediction of the state kernel (kernel-matrix chunks + a GEMM) instead of T fused predictions.
     _GRID_MIN_WORK = 1 << 16      # n_new m T below which the per-time loop runs: launch-bound either way
 
-    def _grid_setup(self, Xnew, times, want_derivative=False):
-        """(state descriptor, [Xnew | 0], E, D or None), or None when the per-time loop has to run."""
+    def _grid_split(self, Xnew, times):
+        """(state descriptor, time leaf, [Xnew | 0]), or None when the per-time loop has to run."""
         from .base_cov import split_state_time
         if isinstance(Xnew, _lib.DeviceArray) or self.weights.ndim != 1 or times.shape[0] < 2:
             return None
@@ -370,7 +370,14 @@ class PredictorTime(Predictor):
         Xq = self._with_time(Xnew, 0.0)            # the loop's own validation; the state factor never reads the time column
         if Xq.shape[0] * self.centers.shape[0] * times.shape[0] < self._GRID_MIN_WORK:
             return None
-        state, time_leaf = split
+        return split[0], split[1], Xq
+
+    def _grid_setup(self, Xnew, times, want_derivative=False):
+        """(state descriptor, [Xnew | 0], E, D or None), or None when the per-time loop has to run."""
+        split = self._grid_split(Xnew, times)
+        if split is None:
+            return None
+        state, time_leaf, Xq = split
         s = np.ascontiguousarray(self.centers[:, -1:])
         K, g = _lib.default_context().leaf_factors(time_leaf, times.reshape(-1, 1), s)        # (T, m) each
         E = np.ascontiguousarray((K * self.weights).T)
@@ -433,6 +440,54 @@ class PredictorTime(Predictor):
             return NotImplemented
         state, Xq, _, D = setup
         return _lib.default_context().predict_mean(state, Xq, self.centers, D, 0.0)
+
+    # The variances on a grid: the kernel row at time t is the state row scaled by S[t, j] = k_time(t, s_j), so
+    # one device call evaluates the state rows once per row chunk, stacks the scaled rows of a block of times into one tall
+    # panel and runs the triangular solve / the product with W once on it -- L, Cs and W go up once, not once per time.
+    _GRID_VARIANCE_DOUBLES = 0           # scratch budget of that call in doubles (0: the library's default, 2^27)
+
+    def _grid_std(self):
+        """The std of W = L^-T diag(std) while L and W are the arrays _attach_uncertainty stored, else None."""
+        rec = getattr(self, "_uncertainty_std", None)
+        if rec is not None and rec[0] is getattr(self, "L", None) and rec[1] is getattr(self, "W", None):
+            return rec[2]
+        return None
+
+    def _grid_variances(self, Xnew, times, diag, want):
+        """The (n, T) arrays named by `want` ("cov", "mcov") from one device call, or NotImplemented when the per-time loop
+        has to run: full matrices (diag=False), a missing factor (the loop raises the predictor's own error), or any of
+        _grid_split's conditions."""
+        if not diag or ("cov" in want and getattr(self, "L", None) is None) \
+                or ("mcov" in want and getattr(self, "W", None) is None):
+            return NotImplemented
+        split = self._grid_split(Xnew, times)
+        if split is None:
+            return NotImplemented
+        state, time_leaf, Xq = split
+        ctx = _lib.default_context()
+        tcol = np.ascontiguousarray(times.reshape(-1, 1))
+        S, _ = ctx.leaf_factors(time_leaf, tcol, np.ascontiguousarray(self.centers[:, -1:]))      # (T, m)
+        kdiag = np.ascontiguousarray(np.diagonal(ctx.leaf_factors(time_leaf, tcol, tcol)[0]))     # k_time(t, t)
+        std = self._grid_std() if "mcov" in want else None
+        return ctx.predict_variance_grid(
+            state, Xq, self.centers, S, kdiag, None if getattr(self, "L", None) is None else np.asarray(self.L),
+            Cs=getattr(self, "Cs", None) if "cov" in want else None,
+            W=np.asarray(self.W) if "mcov" in want and std is None else None, std=std, want=want,
+            scratch_doubles=self._GRID_VARIANCE_DOUBLES)
+
+    def _grid_covariance(self, Xnew, time=None, diag=True, noise_free=False, times=None):
+        if self._has_per_feature_sigma() and not noise_free:
+            return NotImplemented                  # the loop raises the predictor's own error
+        return self._grid_variances(Xnew, times, diag, ("cov",))
+
+    def _grid_mean_covariance(self, Xnew, time=None, diag=True, times=None):
+        return self._grid_variances(Xnew, times, diag, ("mcov",))
+
+    def _grid_uncertainty(self, Xnew, time=None, diag=True, times=None):
+        if self._has_per_feature_sigma():
+            return NotImplemented
+        out = self._grid_variances(Xnew, times, diag, ("cov", "mcov"))
+        return out if out is NotImplemented else out[0] + out[1]
 
     def _with_time(self, Xnew, time):
         Xnew = np.ascontiguousarray(ensure_2d(validate_array(Xnew, "Xnew")), dtype=np.float64)

@@ -218,6 +218,9 @@ def _attach_uncertainty(pred, Lf, std):
     pred.L = Lh
     pred.W = _lib.default_context().trsm_lower(Lh, np.diag(std), trans=True)
     pred._state_variables |= {"L", "W"}
+    # not a state variable (the wire format has L and W only): lets the time-grid variances use sum std^2 (k L^-T)^2 for
+    # |W^T k|^2 while L and W are still these very arrays (PredictorTime._grid_std)
+    pred._uncertainty_std = (pred.L, pred.W, np.ascontiguousarray(std, dtype=np.float64).reshape(-1))
 
 
 class _FullConditional:
