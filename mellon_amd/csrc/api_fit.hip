@@ -528,7 +528,7 @@ extern "C" int mln_fit_gram_rank(mln_fit* f, double tol, int64_t* rank_out, doub
   double lmax = 0.0;
   // The count by inertia (ldl_inertia.hip: Lanczos for lambda_max, then the signs of the pivots of G - x I; ~15 ms at
   // m = 5000) first; where it cannot certify its pivots, the tridiagonal path (0.25 s) on a fresh Gram.
-  const bool ldl_ok = !(mln_experiment("MELLON_AMD_RANK_LDL") && std::atoi(mln_experiment("MELLON_AMD_RANK_LDL")) == 0);
+  const bool ldl_ok = !mln_knob_off("MELLON_AMD_RANK_LDL");
   bool done = false;
   if (rc == MLN_OK && ldl_ok) {
     rc = dev_sym_rank_above_ldl(ctx, G, m, ld, tol * tol, rank_out, &lmax, &done);

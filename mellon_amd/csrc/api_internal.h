@@ -30,7 +30,6 @@
 void fit_events_borrow(mln_ctx* ctx, std::vector<hipEvent_t>* evs);   // api_fit.hip: the context's pool of timing events
 void fit_events_return(mln_ctx* ctx, std::vector<hipEvent_t>* evs);
 
-bool is_device_ptr(const void* p);
 double now_s();
 
 // Read-only input that may live on host or device.

@@ -1,16 +1,24 @@
-// k-means landmarks on the device (reference: mellon/parameters.py:243-291
-// calls sklearn.cluster.k_means(x, m, n_init=1, random_state=...), i.e. k-means++ seeding + Lloyd).
-// Same algorithm family, own implementation: the centroids are NOT bit-compatible with sklearn's
-// (different RNG stream and summation order), so parity tests pass landmarks explicitly; this is
+// k-means landmarks on the device (reference: mellon/parameters.py:243-291 calls sklearn.cluster.k_means(x, m,
+// n_init=1, random_state=...), i.e. k-means++ seeding + Lloyd).  Same algorithm family, own implementation: the centroids are NOT
+// bit-compatible with sklearn's (different RNG stream and summation order), so parity tests pass landmarks explicitly; this is
 // the at-scale path (sklearn needs minutes for 1e6 x 50 cells and 5 000 clusters).
-//
-//   seeding   k-means++ (D^2 sampling): one fused kernel per new centre updates every cell's squared
-//             distance to its closest centre and emits 1024-cell block sums; the host draws the next
-//             centre from them with a seeded xorshift generator (two tiny downloads per centre).
-//   Lloyd     assignment = tiled fp64 distance kernel with running arg-min (the nn_distances tile
-//             structure), update = FIXED-POINT integer atomics into m x d sums (round 4c: any summation order gives
-//             the same bits -- the centres are bit-reproducible), stop when the summed squared centre shift
-//             <= tol * mean feature variance (sklearn's rule) or after max_iter sweeps.
+//   seeding   k-means++ (D^2 sampling), two launches per centre and no download: one kernel updates every cell's squared distance
+//             to its closest centre and emits block sums; one workgroup walks the block sums, then the cells of the chosen block,
+//             to the target the host drew (seeded xorshift, a kernel argument) and writes that cell as the next centre.  From
+//             2^24 cell-centre pairs on (d <= 61) the update reads the half-precision copy of the cells, 256 cells per workgroup
+//             of 1024 threads (eight lanes per cell; small blocks keep the CUs busy on the coarse level); the fp64 update takes
+//             1024 cells per workgroup of 256 threads -- hence nblk_h and nblk, and the two instances of k_seed_select.
+//   sums      FIXED-POINT integer atomics into m x d sums, scaled per column by a power of two: any summation order gives the
+//             same bits -- the centres are bit-reproducible.
+//   Lloyd     stops when the summed squared centre shift <= tol * mean feature variance (sklearn's rule) or after max_iter sweeps;
+//             update, stopping test and final inertia are fp64 on every path.  km_plan picks one of three drivers:
+//     plain     every sweep assigns every cell -- fp64 tiles with a running arg-min (k_assign / k_assign_mfma) or, from 2^24 pairs
+//               on, the fp16-split product (rowmin_f16.hip; MELLON_AMD_KM_FP16=0 disables) -- and downloads the shift
+//     Hamerly   with the folded fp16 product (2^24 pairs, d <= 61): an upper and ONE lower bound per cell; sweep 0 searches every
+//               cell, later sweeps those whose bounds no longer decide; the stopping test stays on the device (_KM_BOUNDS=0: plain)
+//     groups    and m in [1024, 8192], n >= 65536: a lower bound per 256-centre stage, centres ordered by bisection, cells sorted
+//               by first label, so that a block of cells skips whole stages (_KM_PRUNE=0: Hamerly)
+//   levels    mln_kmeans: with many cells per centre, seeding and a first Lloyd run on every s-th cell, then all cells polish
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -783,310 +791,333 @@ static void centre_sweep_order(const double* c, int m, int d, int* order) {
   }
 }
 
-// One level: k-means++ seeding (or the centres in `init`, device, m x d) followed by Lloyd's iterations on the n cells at x.
-static int kmeans_level(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int64_t m, int64_t seed,
-                        int32_t max_iter, double tol, const double* init, double* centers, int32_t* n_iter_out,
-                        double* inertia_out) {
-  hipStream_t st = ctx->stream;
-  // every buffer here is used on st only and st is drained before the function returns: released without the device-wide wait
+// ---- one level: the plan (which path), the workspaces (one per tier of the plan), the stages -------------------------------
+struct KmPlan {
+  // seeded: k-means++ draws (no `init`); prepared: the half-precision copies apply (prep and xxs are made); fold: |c|^2 travels
+  // inside the fp16 operands (d <= 61); seed_h: the seeding reads the fp16 cells; fast_assign: the assignment runs on the matrix
+  // cores; bounds / prune: the sweeps carry Hamerly bounds / group bounds on sorted cells (acted on when max_iter > 0)
+  bool seeded, prepared, fold, seed_h, fast_assign, bounds, prune;
+  int S, nwg;             // 256-centre stages of a sweep; workgroups of the bound kernels
+  int64_t nblk, nblk_h;   // block sums of the fp64 / the half-precision seeding
+};
+static KmPlan km_plan(int64_t n, int d, int64_t m, const double* init) {
+  const bool fp16 = !mln_knob_off("MELLON_AMD_KM_FP16");
+  KmPlan p{};
+  p.seeded = init == nullptr;
+  p.prepared = d <= 64 && n * m >= ((int64_t)1 << 24) && m >= 2;
+  p.fold = d <= 61;
+  p.seed_h = fp16 && p.prepared && p.fold;
+  p.fast_assign = fp16 && p.prepared;
+  // (the bounds' error term needs xxs: `prepared`, which fast_assign implies -- a failed allocation ends the level before)
+  p.bounds = p.fast_assign && p.fold && !mln_knob_off("MELLON_AMD_KM_BOUNDS");
+  p.S = (int)((m + 255) / 256);
+  // group bounds: 1024 to 8192 centres (at most 32 stages), row ids that fit an int
+  p.prune = p.bounds && m >= 1024 && p.S <= 32 && n >= 65536 && n <= 2147483647LL && !mln_knob_off("MELLON_AMD_KM_PRUNE");
+  p.nwg = (int)((n + KB_ROWS - 1) / KB_ROWS);
+  p.nblk = (n + SBLK - 1) / SBLK;
+  p.nblk_h = (n + 255) / 256;
+  return p;
+}
+// (buffer, count, name) triples, allocated in order; the first failure ends it
+template <class B, class... Rest>
+static int alloc_all(mln_ctx* ctx, B& buf, size_t count, const char* what, Rest&&... rest) {
+  MLN_TRY(buf.alloc(ctx, count, what));
+  if constexpr (sizeof...(rest) > 0) return alloc_all(ctx, rest...);
+  return MLN_OK;
+}
+// Every buffer of a level is used on ctx->stream only, and the level drains that stream before any of them is released
+// (DrainOnExit): StreamBuf, released without the device-wide wait.  A tier the plan does not need stays empty.
+struct KmCommon {
   StreamBuf<double> dx_own, dc, xx, cc, mind, bsum, sums, counts, shift;
+  StreamBuf<unsigned long long> colmax;      // fixed-point cluster sums: per-column magnitudes (+ the non-finite flag) ->
+  StreamBuf<double> colscale, sq;            // power-of-two scales [0, d), inverses [d, 2d); sq: |shift|^2 per centre, d variances
   StreamBuf<int> label;
   StreamBuf<int64_t> pick;
-  double* dx = const_cast<double*>(x);
-  hipPointerAttribute_t attr;
-  if (!(hipPointerGetAttributes(&attr, x) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))) {
-    (void)hipGetLastError();
-    MLN_TRY(dx_own.alloc(ctx, (size_t)n * d, "dx"));
-    dx = dx_own;
+  int alloc(mln_ctx* ctx, const KmPlan& p, size_t n, size_t d, size_t m) {
+    return alloc_all(ctx, dc, m * d, "dc", xx, n, "xx", cc, m, "cc", mind, n, "mind", bsum, (size_t)p.nblk_h, "bsum", sums, m * d, "sums",
+                     counts, m, "counts", shift, 1, "shift", colmax, d + 1, "colmax", colscale, 2 * d, "colscale", sq, m > d ? m : d, "sq",
+                     label, n, "label", pick, 1, "pick");
   }
-  const int64_t nblk = (n + SBLK - 1) / SBLK, nblk_h = (n + 255) / 256;     // (block sums of the fp64 / the half-precision seeding)
-  MLN_TRY(dc.alloc(ctx, (size_t)m * d, "dc"));
-  MLN_TRY(xx.alloc(ctx, (size_t)n, "xx"));
-  MLN_TRY(cc.alloc(ctx, (size_t)m, "cc"));
-  MLN_TRY(mind.alloc(ctx, (size_t)n, "mind"));
-  MLN_TRY(bsum.alloc(ctx, (size_t)nblk_h, "bsum"));
-  MLN_TRY(sums.alloc(ctx, (size_t)m * d, "sums"));
-  MLN_TRY(counts.alloc(ctx, (size_t)m, "counts"));
-  MLN_TRY(shift.alloc(ctx, 1, "shift"));
-  // fixed-point cluster sums: per-column magnitudes -> power-of-two scales [0, d) and their inverses [d, 2d); sq: |shift|^2 per centre
-  StreamBuf<unsigned long long> colmax;
-  StreamBuf<double> colscale, sq;
-  MLN_TRY(colmax.alloc(ctx, (size_t)(d + 1), "colmax"));
-  MLN_TRY(colscale.alloc(ctx, 2 * (size_t)d, "colscale"));
-  MLN_TRY(sq.alloc(ctx, (size_t)(m > d ? m : d), "sq"));     // (also the d column variances)
-  MLN_TRY(label.alloc(ctx, (size_t)n, "label"));
-  MLN_TRY(pick.alloc(ctx, 1, "pick"));
-  // (the upload is enqueued after the allocations: an early return above leaves nothing in flight on st)
-  if (dx_own) MLN_HIP(ctx, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st));
-  int rc = MLN_OK;
-  auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "kmeans", __FILE__, __LINE__); };
-
-  chk(hipMemsetAsync(colmax, 0, sizeof(unsigned long long) * (size_t)(d + 1), st));
-  if (rc == MLN_OK) {
-    hipLaunchKernelGGL(k_km_colmax, dim3(1024), dim3(256), 0, st, dx, n, d, colmax);
-    hipLaunchKernelGGL(k_km_colscale, dim3(1), dim3(256), 0, st, colmax, d, n, colscale);
-    unsigned long long bad = 0;
-    chk(hipMemcpyAsync(&bad, colmax + d, sizeof(bad), hipMemcpyDeviceToHost, st));
-    chk(hipStreamSynchronize(st));
-    if (rc == MLN_OK && bad) { mln_set_error(ctx, "kmeans: x holds non-finite values"); rc = MLN_ERR_ARG; }
-  }
-  // ---- k-means++ seeding ------------------------------------------------------------------------
-  // m - 1 sequential draws, each after one update of every cell's distance to its nearest centre so far.  Everything stays
-  // on the device (the uniform draws are uploaded once); large problems read the half-precision copy of the cells.
-  XorShift rng((unsigned long long)seed);
-  int64_t cur = (int64_t)(rng.uniform() * (double)n);
-  if (cur >= n) cur = n - 1;
-  const bool seeded = init == nullptr;
-  const bool km_fp16_seed = !(mln_experiment("MELLON_AMD_KM_FP16") && std::atoi(mln_experiment("MELLON_AMD_KM_FP16")) == 0);
-  const bool seed_h = km_fp16_seed && d <= 61 && n * m >= ((int64_t)1 << 24) && m >= 2;
-  StreamBuf<char> xsplit;
-  StreamBuf<double> prep;          // centre and scale of the half-precision copies (rowmin_prepare)
-  if (d <= 64 && n * m >= ((int64_t)1 << 24) && m >= 2 && rc == MLN_OK) {
-    if (rc == MLN_OK) rc = prep.alloc(ctx, ROWMIN_PREP_DOUBLES, "prep");
-    if (rc == MLN_OK) rc = rowmin_prepare(ctx, dx, n, nullptr, 0, d, prep);
-  }
-  StreamBuf<double> xxs;         // squared norms of the centred, scaled cells (the error bound of the fp16 sweep needs them)
-  if (prep && rc == MLN_OK) rc = xxs.alloc(ctx, (size_t)n, "xxs");
-  if (seed_h && rc == MLN_OK) {
-    rc = xsplit.alloc(ctx, rowmin_split_bytes(n), "xsplit");
-    if (rc == MLN_OK) rc = launch_split_f16(ctx, dx, n, d, xsplit, xxs, nullptr, 1, prep);   // role 1: -2 x (also the Lloyd sweeps' operand)
-  }
-  if (rc == MLN_OK && seeded) chk(hipMemcpyAsync(dc, dx + cur * d, sizeof(double) * d, hipMemcpyDeviceToDevice, st));
-  if (rc == MLN_OK && !seeded) chk(hipMemcpyAsync(dc, init, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToDevice, st));
-  for (int64_t j = 0; seeded && j + 1 < m && rc == MLN_OK; ++j) {
-    if (seed_h) {
-      hipLaunchKernelGGL((k_seed_update_h<256>), dim3((unsigned)nblk_h), dim3(1024), 0, st, reinterpret_cast<const _Float16*>(xsplit.get()), n, d,
-                         -0.5f, dc + j * d, prep, mind, bsum, j == 0 ? 1 : 0);
-      hipLaunchKernelGGL((k_seed_select<256>), dim3(1), dim3(256), 0, st, bsum, nblk_h, mind, n, rng.uniform(), dx, d, dc + (j + 1) * d);
-    } else {
-      hipLaunchKernelGGL(k_seed_update, dim3((unsigned)nblk), dim3(256), 0, st, dx, n, d, dc + j * d, mind, bsum, j == 0 ? 1 : 0);
-      hipLaunchKernelGGL((k_seed_select<SBLK>), dim3(1), dim3(256), 0, st, bsum, nblk, mind, n, rng.uniform(), dx, d, dc + (j + 1) * d);
-    }
-    if ((j & 1023) == 1023) chk(hipStreamSynchronize(st));     // (bounds the launch queue)
-  }
-  chk(hipGetLastError());
-
-  // ---- Lloyd ------------------------------------------------------------------------------------------
-  // tolerance scaled like sklearn: tol * mean over features of the feature variance
-  double scaled_tol = 0.0;
-  if (rc == MLN_OK) {
-    const int64_t ns = (n < 200000) ? n : 200000;   // variance estimate from an evenly spaced subset (on the device: the
-    const int64_t stride = n / ns;                   // 32 MB copy to the host and its loops were 8-14 ms per level)
-    std::vector<double> hv((size_t)d);
-    hipLaunchKernelGGL(k_km_col_var, dim3((unsigned)d), dim3(1024), 0, st, dx, ns, stride, d, sq);     // (sq: max(m, d) doubles)
-    chk(hipMemcpyAsync(hv.data(), sq, sizeof(double) * (size_t)d, hipMemcpyDeviceToHost, st));
-    chk(hipStreamSynchronize(st));
-    double var_sum = 0.0;
-    for (int k = 0; k < d; ++k) var_sum += hv[(size_t)k];
-    scaled_tol = tol * var_sum / d;
-  }
-  int it = 0;
-  hipLaunchKernelGGL(k_sqnorm_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx, n, d, xx);
-  // Assignment on the fp16 matrix cores (rowmin_f16.hip: cells and centres split into hi + lo halves, three products,
-  // fp32 accumulation: distances to ~1e-5 relative).  A cell whose two nearest centres tie within that may land on
-  // either -- k-means is indifferent -- and the centre update, the stopping test and the final inertia stay fp64.
-  // 5e11 fp64 flops per sweep at 1e6 cells x 5000 centres (15 ms) become ~1 ms.  MELLON_AMD_KM_FP16=0 disables.
-  const bool km_fp16 = !(mln_experiment("MELLON_AMD_KM_FP16") && std::atoi(mln_experiment("MELLON_AMD_KM_FP16")) == 0);
-  const bool fast_assign = km_fp16 && d <= 64 && n * m >= ((int64_t)1 << 24) && m >= 2;
-  const bool km_fold = d <= 61;
-  StreamBuf<char> csplit;
+};
+struct KmHalf {                              // operands of the fp16 matrix cores (rowmin_f16.hip)
+  StreamBuf<double> prep, xxs;               // centre and scale of the copies (rowmin_prepare); |x|^2 of the centred, scaled cells
+  StreamBuf<char> xsplit, csplit;
   StreamBuf<float> ccf, m1f;
-  if (fast_assign && rc == MLN_OK) {
-    const bool have = (bool)xsplit;            // (the seeding's copy has role 1: right for the folded product)
-    if (!have) rc = xsplit.alloc(ctx, rowmin_split_bytes(n), "xsplit");
-    if (rc == MLN_OK) rc = csplit.alloc(ctx, rowmin_split_bytes(m), "csplit");
-    if (rc == MLN_OK) rc = ccf.alloc(ctx, (size_t)m, "ccf");
-    if (rc == MLN_OK) rc = m1f.alloc(ctx, (size_t)n, "m1f");
-    if (rc == MLN_OK && !have) rc = launch_split_f16(ctx, dx, n, d, xsplit, xxs, nullptr, km_fold ? 1 : 0, prep);
+  int alloc(mln_ctx* ctx, const KmPlan& p, size_t n, size_t m) {
+    if (p.prepared) MLN_TRY(alloc_all(ctx, prep, ROWMIN_PREP_DOUBLES, "prep", xxs, n, "xxs"));
+    if (!p.fast_assign) return MLN_OK;
+    return alloc_all(ctx, xsplit, rowmin_split_bytes(n), "xsplit", csplit, rowmin_split_bytes(m), "csplit", ccf, m, "ccf", m1f, n, "m1f");
   }
-  // With the folded fp16 sweep available the iterations carry distance bounds (see k_km_bounds): sweep 0 searches every
-  // cell, later sweeps only the cells whose bounds no longer decide; the sums of the clusters follow the cells that moved.
-  const bool km_bounds = fast_assign && km_fold && xxs && !(mln_experiment("MELLON_AMD_KM_BOUNDS") && std::atoi(mln_experiment("MELLON_AMD_KM_BOUNDS")) == 0);
+};
+struct KmHamerly {                           // bounds of every cell, movement of every centre, the list of open rows
   StreamBuf<double> ub, lb, delta, dstat, yy, ymax;
   StreamBuf<float> m2f;
-  StreamBuf<int> argc, nflag, flagged;
-  if (km_bounds && rc == MLN_OK) {
-    if (rc == MLN_OK) rc = ub.alloc(ctx, (size_t)n, "ub");
-    if (rc == MLN_OK) rc = lb.alloc(ctx, (size_t)n, "lb");
-    if (rc == MLN_OK) rc = delta.alloc(ctx, (size_t)m, "delta");
-    if (rc == MLN_OK) rc = dstat.alloc(ctx, 4, "dstat");
-    if (rc == MLN_OK) rc = yy.alloc(ctx, (size_t)m, "yy");
-    if (rc == MLN_OK) rc = ymax.alloc(ctx, 1, "ymax");
-    if (rc == MLN_OK) rc = m2f.alloc(ctx, (size_t)n, "m2f");
-    if (rc == MLN_OK) rc = argc.alloc(ctx, (size_t)n, "argc");
-    if (rc == MLN_OK) rc = nflag.alloc(ctx, 1, "nflag");
-    if (rc == MLN_OK) rc = flagged.alloc(ctx, (size_t)n, "flagged");
+  StreamBuf<int> argc, nflag, flagged, kstate, wg_count, wg_off, flagged_tmp;
+  int alloc(mln_ctx* ctx, const KmPlan& p, size_t n, size_t m) {
+    if (!p.bounds) return MLN_OK;
+    MLN_TRY(alloc_all(ctx, ub, n, "ub", lb, n, "lb", delta, m, "delta", dstat, 4, "dstat", yy, m, "yy", ymax, 1, "ymax", m2f, n, "m2f",
+                      argc, n, "argc", nflag, 1, "nflag", flagged, n, "flagged", wg_count, (size_t)p.nwg, "wg_count",
+                      wg_off, (size_t)p.nwg, "wg_off", flagged_tmp, (size_t)p.nwg * KB_ROWS, "flagged_tmp"));
+    return kstate.alloc_zeroed(ctx, 2, "kstate");          // {converged, sweeps done}
   }
-  // Group bounds (see k_km_gather_centres): 1024 to 8192 centres (at most 32 stages).  MELLON_AMD_KM_PRUNE=0 disables.
-  const int S = (int)((m + 255) / 256);
-  const bool km_prune = km_bounds && m >= 1024 && S <= 32 && n >= 65536 && n <= 2147483647LL &&
-                        !(mln_experiment("MELLON_AMD_KM_PRUNE") && std::atoi(mln_experiment("MELLON_AMD_KM_PRUNE")) == 0);
-  StreamBuf<int> kstate, wg_count, wg_off, flagged_tmp, cperm, cposd, perm, label_s;
+};
+struct KmGroupBufs {                         // group bounds: centres and cells in sweep order, bounds and minima per stage
+  StreamBuf<int> cperm, cposd, perm, label_s;
   StreamBuf<double> dcp, cum, dxs, ub_s, lb_s;
   StreamBuf<float> lbg, smin;
   StreamBuf<uint32_t> smask, rowmask;
-  const int nwg = (int)((n + KB_ROWS - 1) / KB_ROWS);
-  if (km_bounds && rc == MLN_OK) {
-    if (rc == MLN_OK) rc = kstate.alloc(ctx, 2, "kstate");
-    if (rc == MLN_OK) rc = wg_count.alloc(ctx, (size_t)nwg, "wg_count");
-    if (rc == MLN_OK) rc = wg_off.alloc(ctx, (size_t)nwg, "wg_off");
-    if (rc == MLN_OK) rc = flagged_tmp.alloc(ctx, (size_t)nwg * KB_ROWS, "flagged_tmp");
-    if (rc == MLN_OK) chk(hipMemsetAsync(kstate, 0, sizeof(int) * 2, st));
+  std::vector<int> h_order, h_cpos;          // host copies of cperm, cposd (members: they outlive their two uploads)
+  int alloc(mln_ctx* ctx, const KmPlan& p, size_t n, size_t d, size_t m) {
+    if (!p.prune) return MLN_OK;
+    MLN_TRY(alloc_all(ctx, cperm, m, "cperm", cposd, m, "cposd", perm, n, "perm", label_s, n, "label_s", ub_s, n, "ub_s", lb_s, n, "lb_s",
+                      dcp, m * d, "dcp", dxs, n * d, "dxs", lbg, n * p.S, "lbg", smin, n * p.S, "smin", smask, (n + 255) / 256, "smask",
+                      rowmask, n, "rowmask"));
+    return cum.alloc_zeroed(ctx, (size_t)p.S, "cum");
   }
-  if (km_prune && rc == MLN_OK) {
-    if (rc == MLN_OK) rc = cperm.alloc(ctx, (size_t)m, "cperm");
-    if (rc == MLN_OK) rc = cposd.alloc(ctx, (size_t)m, "cposd");
-    if (rc == MLN_OK) rc = perm.alloc(ctx, (size_t)n, "perm");
-    if (rc == MLN_OK) rc = label_s.alloc(ctx, (size_t)n, "label_s");
-    if (rc == MLN_OK) rc = ub_s.alloc(ctx, (size_t)n, "ub_s");
-    if (rc == MLN_OK) rc = lb_s.alloc(ctx, (size_t)n, "lb_s");
-    if (rc == MLN_OK) rc = dcp.alloc(ctx, (size_t)m * d, "dcp");
-    if (rc == MLN_OK) rc = cum.alloc(ctx, (size_t)S, "cum");
-    if (rc == MLN_OK) rc = dxs.alloc(ctx, (size_t)n * d, "dxs");
-    if (rc == MLN_OK) rc = lbg.alloc(ctx, (size_t)n * S, "lbg");
-    if (rc == MLN_OK) rc = smin.alloc(ctx, (size_t)n * S, "smin");
-    if (rc == MLN_OK) rc = smask.alloc(ctx, (size_t)((n + 255) / 256), "smask");
-    if (rc == MLN_OK) rc = rowmask.alloc(ctx, (size_t)n, "rowmask");
-    if (rc == MLN_OK) chk(hipMemsetAsync(cum, 0, sizeof(double) * (size_t)S, st));
+};
+struct DrainOnExit { hipStream_t st; ~DrainOnExit() { (void)hipStreamSynchronize(st); } };
+// x where kernels can read it: x itself when it is device memory, else a copy in `owned`, uploaded on ctx->stream
+template <class Buf>
+static int cells_on_device(mln_ctx* ctx, const double* x, size_t count, Buf& owned, const char* what, const double** dx) {
+  if (is_device_ptr(x)) { *dx = x; return MLN_OK; }
+  MLN_TRY(owned.alloc(ctx, count, what));
+  *dx = owned;
+  MLN_HIP(ctx, hipMemcpyAsync(owned, x, sizeof(double) * count, hipMemcpyHostToDevice, ctx->stream));
+  return MLN_OK;
+}
+
+struct KmLevel {                             // one level's state and its stages; each returns the first error, launching nothing after it
+  mln_ctx* ctx; hipStream_t st;
+  int64_t n, m; int d; KmPlan plan;
+  const double* dx = nullptr;                // the cells on the device
+  KmCommon w; KmHalf h; KmHamerly b; KmGroupBufs g;
+  // the cells on the device, the column scales of the fixed-point sums, and no NaN / inf among the cells
+  int input(const double* x) {
+    MLN_TRY(cells_on_device(ctx, x, (size_t)n * d, w.dx_own, "dx", &dx));
+    MLN_HIP(ctx, hipMemsetAsync(w.colmax, 0, sizeof(unsigned long long) * (size_t)(d + 1), st));
+    hipLaunchKernelGGL(k_km_colmax, dim3(1024), dim3(256), 0, st, dx, n, d, w.colmax);
+    hipLaunchKernelGGL(k_km_colscale, dim3(1), dim3(256), 0, st, w.colmax, d, n, w.colscale);
+    unsigned long long bad = 0;
+    MLN_HIP(ctx, hipMemcpyAsync(&bad, w.colmax + d, sizeof(bad), hipMemcpyDeviceToHost, st));
+    MLN_HIP(ctx, hipStreamSynchronize(st));
+    if (bad) { mln_set_error(ctx, "kmeans: x holds non-finite values"); return MLN_ERR_ARG; }
+    return MLN_OK;
   }
-  if (km_bounds && rc == MLN_OK && max_iter > 0) {
-    const double* xl = dx;        // the cells in the order the sweeps walk them (sorted by first label with group bounds)
-    bool groups = false;
-    KmGroups grp{lbg, cum, smin, n, cposd, S};
-    // the part of a sweep after the assignment: new centres, their movement, the bounds, the list of open rows
-    auto tail = [&]() {
-      chk(hipMemsetAsync(shift, 0, sizeof(double), st));
-      hipLaunchKernelGGL(k_finish, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, dc, sums, counts, m, d, sq, delta, colscale);
-      hipLaunchKernelGGL(k_km_sum_fixed, dim3(1), dim3(256), 0, st, sq, m, shift, scaled_tol, kstate);
-      if (groups) {
-        hipLaunchKernelGGL(k_km_stage_delta, dim3((unsigned)S), dim3(256), 0, st, delta, cperm, m, cum);
-        hipLaunchKernelGGL(k_km_bounds_g, dim3((unsigned)nwg), dim3(256), 0, st, xl, n, d, dc, label, ub, lbg, cum, S, cposd, kstate, wg_count,
-                           flagged_tmp, rowmask);
+  // k-means++ seeding: m - 1 sequential draws, each after one update of every cell's distance to its nearest centre so far.
+  // Everything stays on the device; large problems read the half-precision copy of the cells (made here, role 1: -2 x, also
+  // the operand of the folded Lloyd sweeps).  With `init` (device, m x d) the centres are copied instead.
+  int seed(int64_t rng_seed, const double* init) {
+    double* dc = w.dc;
+    XorShift rng((unsigned long long)rng_seed);
+    int64_t cur = (int64_t)(rng.uniform() * (double)n);
+    if (cur >= n) cur = n - 1;
+    if (plan.prepared) MLN_TRY(rowmin_prepare(ctx, dx, n, nullptr, 0, d, h.prep));
+    if (plan.seed_h) MLN_TRY(launch_split_f16(ctx, dx, n, d, h.xsplit, h.xxs, nullptr, 1, h.prep));
+    if (!plan.seeded) MLN_HIP(ctx, hipMemcpyAsync(dc, init, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToDevice, st));
+    else MLN_HIP(ctx, hipMemcpyAsync(dc, dx + cur * d, sizeof(double) * d, hipMemcpyDeviceToDevice, st));
+    for (int64_t j = 0; plan.seeded && j + 1 < m; ++j) {
+      if (plan.seed_h) {
+        hipLaunchKernelGGL((k_seed_update_h<256>), dim3((unsigned)plan.nblk_h), dim3(1024), 0, st, reinterpret_cast<const _Float16*>(h.xsplit.get()),
+                           n, d, -0.5f, dc + j * d, h.prep, w.mind, w.bsum, j == 0 ? 1 : 0);
+        hipLaunchKernelGGL((k_seed_select<256>), dim3(1), dim3(256), 0, st, w.bsum, plan.nblk_h, w.mind, n, rng.uniform(), dx, d, dc + (j + 1) * d);
       } else {
-        hipLaunchKernelGGL(k_km_delta_stats, dim3(1), dim3(256), 0, st, delta, m, dstat);
-        hipLaunchKernelGGL(k_km_bounds, dim3((unsigned)nwg), dim3(256), 0, st, xl, n, d, dc, label, ub, lb, delta, dstat, kstate, wg_count,
-                           flagged_tmp);
+        hipLaunchKernelGGL(k_seed_update, dim3((unsigned)plan.nblk), dim3(256), 0, st, dx, n, d, dc + j * d, w.mind, w.bsum, j == 0 ? 1 : 0);
+        hipLaunchKernelGGL((k_seed_select<SBLK>), dim3(1), dim3(256), 0, st, w.bsum, plan.nblk, w.mind, n, rng.uniform(), dx, d, dc + (j + 1) * d);
       }
-      hipLaunchKernelGGL(k_km_flag_scan, dim3(1), dim3(1024), 0, st, wg_count, nwg, wg_off, nflag);
-      hipLaunchKernelGGL(k_km_flag_compact, dim3((unsigned)nwg), dim3(256), 0, st, flagged_tmp, wg_count, wg_off, flagged);
-    };
-    // ---- sweep 0: every cell against every centre (with group bounds: the centres already in their sweep order)
-    if (km_prune) {
-      std::vector<double> hc((size_t)m * d);
-      std::vector<int> order((size_t)m), cpos((size_t)m);
-      chk(hipMemcpyAsync(hc.data(), dc, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToHost, st));
-      chk(hipStreamSynchronize(st));
-      if (rc == MLN_OK) {
-        centre_sweep_order(hc.data(), (int)m, d, order.data());
-        for (int p = 0; p < (int)m; ++p) cpos[(size_t)order[p]] = p;
-        chk(hipMemcpyAsync(cperm, order.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(cposd, cpos.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st));
-        chk(hipStreamSynchronize(st));
-        groups = rc == MLN_OK;
-      }
+      if ((j & 1023) == 1023) MLN_HIP(ctx, hipStreamSynchronize(st));     // (bounds the launch queue)
     }
-    auto centres_split = [&]() {
-      if (groups) hipLaunchKernelGGL(k_km_gather_centres, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0, st, dc, cperm, m, d, dcp);
-      int r = launch_split_f16(ctx, groups ? dcp : dc, m, d, csplit, yy, ccf, 2, prep);
-      if (r == MLN_OK) r = launch_max_norm(ctx, yy, m, ymax);
-      return r;
-    };
-    if (rc == MLN_OK) rc = centres_split();
-    if (rc == MLN_OK) rc = launch_rowmin_masked(ctx, xsplit, n, nullptr, csplit, m, m1f, m2f, argc, nullptr, nullptr, 0);
-    if (rc == MLN_OK) rc = launch_km_resolve(ctx, dx, n, nullptr, dc, m, d, xxs, ymax, prep, m2f, argc, label, ub, lb, nullptr, nullptr, colscale,
-                                             nullptr, groups ? cperm : nullptr);
-    if (groups && rc == MLN_OK) {
-      // the order of the cells (a stable counting sort of the n first labels by sweep position: the same order from run to
-      // run), once per call; then the stage minima of every cell and the first group bounds
-      std::vector<int> hl((size_t)n), hpos((size_t)m), hperm((size_t)n);
-      chk(hipMemcpyAsync(hl.data(), label, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
-      chk(hipMemcpyAsync(hpos.data(), cposd, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, st));
-      chk(hipStreamSynchronize(st));
-      if (rc == MLN_OK) {
-        std::vector<int64_t> start((size_t)m + 1, 0);
-        for (int64_t i = 0; i < n; ++i) start[(size_t)hpos[(size_t)hl[(size_t)i]] + 1]++;
-        for (int64_t p = 0; p < m; ++p) start[(size_t)p + 1] += start[(size_t)p];
-        for (int64_t i = 0; i < n; ++i) hperm[(size_t)start[(size_t)hpos[(size_t)hl[(size_t)i]]]++] = (int)i;
-        chk(hipMemcpyAsync(perm, hperm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_km_gather_rows, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, st, dx, perm, n, d, dxs);
-        hipLaunchKernelGGL(k_km_gather_state, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, perm, n, label, ub, lb, label_s, ub_s, lb_s);
-        chk(hipStreamSynchronize(st));                      // (the host vector above is the copy's source)
-        if (rc == MLN_OK) rc = launch_split_f16(ctx, dxs, n, d, xsplit, xxs, nullptr, 1, prep);      // the same rows, in the new order
-        std::swap(label, label_s); std::swap(ub, ub_s); std::swap(lb, lb_s);
-        xl = dxs;
-        if (rc == MLN_OK) rc = launch_rowmin_masked(ctx, xsplit, n, nullptr, csplit, m, nullptr, nullptr, nullptr, nullptr, nullptr, 0, smin, n);
-        if (rc == MLN_OK) rc = launch_km_init_groups(ctx, n, label, lb, xxs, ymax, prep, &grp);
-      }
-    }
-    if (rc == MLN_OK) {
-      chk(hipMemsetAsync(sums, 0, sizeof(double) * (size_t)m * d, st));
-      chk(hipMemsetAsync(counts, 0, sizeof(double) * (size_t)m, st));
-      hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n + 3) / 4)), dim3(64, 4), 0, st, xl, n, d, label, sums, counts, colscale);
-      tail();
-    }
-    // ---- the sweeps over the open rows, queued eight at a time: their number (nflag) and the stopping test (kstate) stay
-    // on the device -- a sweep behind the converged one finds no open row and moves nothing
-    while (rc == MLN_OK) {
-      int hk[2] = {0, 0};
-      chk(hipMemcpyAsync(hk, kstate, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
-      chk(hipStreamSynchronize(st));
-      it = hk[1];
-      if (rc != MLN_OK || hk[0] || it >= max_iter) break;
-      const int batch = (max_iter - it < 8) ? max_iter - it : 8;
-      for (int b = 0; b < batch && rc == MLN_OK; ++b) {
-        rc = centres_split();
-        if (groups)
-          hipLaunchKernelGGL(k_km_block_mask_g, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, flagged, nflag, rowmask, smask);
-        if (rc == MLN_OK) rc = launch_rowmin_masked(ctx, xsplit, n, nflag, csplit, m, m1f, m2f, argc, flagged, groups ? smask : nullptr,
-                                                    groups ? 1 : 0, groups ? smin : nullptr, n);       // (winner and stage minima in one sweep)
-        if (rc == MLN_OK) rc = launch_km_resolve(ctx, xl, n, flagged, dc, m, d, xxs, ymax, prep, m2f, argc, label, ub, lb, sums, counts,
-                                                 colscale, nflag, groups ? cperm : nullptr, groups ? &grp : nullptr, groups ? smask : nullptr, 1);
-        if (rc == MLN_OK) tail();
-      }
-    }
-  } else
-  for (; it < max_iter && rc == MLN_OK; ++it) {
-    hipLaunchKernelGGL(k_sqnorm_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, dc, m, d, cc);
-    if (fast_assign) {
-      rc = launch_split_f16(ctx, dc, m, d, csplit, nullptr, ccf, km_fold ? 2 : 0, prep);
-      if (rc == MLN_OK) rc = launch_rowmin_f16x3(ctx, xsplit, n, csplit, m, ccf, 0, 0, m1f, nullptr, label, km_fold ? 1 : 0);
-      if (rc != MLN_OK) break;
-    } else if (d <= 64 && n * m >= 4096)
-      hipLaunchKernelGGL(k_assign_mfma, dim3((unsigned)((n + 127) / 128)), dim3(512), 0, st, dx, n, dc, m, d, xx, cc, label, mind);
-    else
-      hipLaunchKernelGGL(k_assign, dim3((unsigned)((n + TM - 1) / TM)), dim3(256), 0, st, dx, n, dc, m, d, xx, cc, label, mind);
-    chk(hipMemsetAsync(sums, 0, sizeof(double) * (size_t)m * d, st));
-    chk(hipMemsetAsync(counts, 0, sizeof(double) * (size_t)m, st));
-    chk(hipMemsetAsync(shift, 0, sizeof(double), st));
-    hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n + 3) / 4)), dim3(64, 4), 0, st, dx, n, d, label, sums, counts, colscale);
-    hipLaunchKernelGGL(k_finish, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, dc, sums, counts, m, d, sq, (double*)nullptr, colscale);
-    hipLaunchKernelGGL(k_km_sum_fixed, dim3(1), dim3(256), 0, st, sq, m, shift, 0.0, (int*)nullptr);
-    double hs = 0.0;
-    chk(hipMemcpyAsync(&hs, shift, sizeof(double), hipMemcpyDeviceToHost, st));
-    chk(hipStreamSynchronize(st));
-    if (hs <= scaled_tol) { ++it; break; }
+    MLN_HIP(ctx, hipGetLastError());
+    return MLN_OK;
   }
-  if (rc == MLN_OK && inertia_out) {   // sum of squared distances to the closest final centre
-    hipLaunchKernelGGL(k_sqnorm_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, dc, m, d, cc);
+  // the tolerance scaled like sklearn's: tol * mean over the features of the feature variance (from an evenly spaced subset, on
+  // the device); then what the sweeps read besides the centres: |x|^2 and, unless the seeding made it, the fp16 split
+  int tolerance(double tol, double* scaled_tol) {
+    const int64_t ns = (n < 200000) ? n : 200000, stride = n / ns;
+    std::vector<double> hv((size_t)d);
+    hipLaunchKernelGGL(k_km_col_var, dim3((unsigned)d), dim3(1024), 0, st, dx, ns, stride, d, w.sq);
+    MLN_HIP(ctx, hipMemcpyAsync(hv.data(), w.sq, sizeof(double) * (size_t)d, hipMemcpyDeviceToHost, st));
+    MLN_HIP(ctx, hipStreamSynchronize(st));
+    double var_sum = 0.0;
+    for (int k = 0; k < d; ++k) var_sum += hv[(size_t)k];
+    *scaled_tol = tol * var_sum / d;
+    hipLaunchKernelGGL(k_sqnorm_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx, n, d, w.xx);
+    if (plan.fast_assign && !plan.seed_h) MLN_TRY(launch_split_f16(ctx, dx, n, d, h.xsplit, h.xxs, nullptr, plan.fold ? 1 : 0, h.prep));
+    return MLN_OK;
+  }
+  // the exact fp64 assignment of every cell (label, squared distance in mind) to the centres whose |c|^2 is in cc
+  void assign_exact() {
     if (d <= 64 && n * m >= 4096)
-      hipLaunchKernelGGL(k_assign_mfma, dim3((unsigned)((n + 127) / 128)), dim3(512), 0, st, dx, n, dc, m, d, xx, cc, label, mind);
+      hipLaunchKernelGGL(k_assign_mfma, dim3((unsigned)((n + 127) / 128)), dim3(512), 0, st, dx, n, w.dc, m, d, w.xx, w.cc, w.label, w.mind);
     else
-      hipLaunchKernelGGL(k_assign, dim3((unsigned)((n + TM - 1) / TM)), dim3(256), 0, st, dx, n, dc, m, d, xx, cc, label, mind);
+      hipLaunchKernelGGL(k_assign, dim3((unsigned)((n + TM - 1) / TM)), dim3(256), 0, st, dx, n, w.dc, m, d, w.xx, w.cc, w.label, w.mind);
+  }
+  // Lloyd, plain: every sweep assigns every cell and one download decides.  On the fp16 matrix cores (rowmin_f16.hip: hi + lo halves,
+  // three products, fp32 sums: distances to ~1e-5 relative) a cell whose two nearest centres tie within that may land on either.
+  int lloyd_plain(int max_iter, double scaled_tol, int* it) {
+    const int fold = plan.fold ? 1 : 0;
+    for (*it = 0; *it < max_iter;) {
+      hipLaunchKernelGGL(k_sqnorm_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.dc, m, d, w.cc);
+      if (plan.fast_assign) {
+        MLN_TRY(launch_split_f16(ctx, w.dc, m, d, h.csplit, nullptr, h.ccf, 2 * fold, h.prep));
+        MLN_TRY(launch_rowmin_f16x3(ctx, h.xsplit, n, h.csplit, m, h.ccf, 0, 0, h.m1f, nullptr, w.label, fold));
+      } else
+        assign_exact();
+      MLN_HIP(ctx, hipMemsetAsync(w.sums, 0, sizeof(double) * (size_t)m * d, st));
+      MLN_HIP(ctx, hipMemsetAsync(w.counts, 0, sizeof(double) * (size_t)m, st));
+      MLN_HIP(ctx, hipMemsetAsync(w.shift, 0, sizeof(double), st));
+      hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n + 3) / 4)), dim3(64, 4), 0, st, dx, n, d, w.label, w.sums, w.counts, w.colscale);
+      hipLaunchKernelGGL(k_finish, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.dc, w.sums, w.counts, m, d, w.sq, (double*)nullptr, w.colscale);
+      hipLaunchKernelGGL(k_km_sum_fixed, dim3(1), dim3(256), 0, st, w.sq, m, w.shift, 0.0, (int*)nullptr);
+      double hs = 0.0;
+      MLN_HIP(ctx, hipMemcpyAsync(&hs, w.shift, sizeof(double), hipMemcpyDeviceToHost, st));
+      MLN_HIP(ctx, hipStreamSynchronize(st));
+      ++*it;
+      if (hs <= scaled_tol) break;
+    }
+    return MLN_OK;
+  }
+  // ---- Lloyd with bounds (see k_km_bounds, k_km_gather_centres): sweep 0 searches every cell, later sweeps only the cells whose
+  // bounds no longer decide; the sums of the clusters follow the cells that moved.  `groups`: group bounds, the centres (and after
+  // the set-up the cells, xl) in sweep order.
+  int centres_split(bool groups) {
+    if (groups) hipLaunchKernelGGL(k_km_gather_centres, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0, st, w.dc, g.cperm, m, d, g.dcp);
+    MLN_TRY(launch_split_f16(ctx, groups ? g.dcp : w.dc, m, d, h.csplit, b.yy, h.ccf, 2, h.prep));
+    return launch_max_norm(ctx, b.yy, m, b.ymax);
+  }
+  int sweep0(bool groups) {                  // every cell against every centre
+    MLN_TRY(centres_split(groups));
+    MLN_TRY(launch_rowmin_masked(ctx, h.xsplit, n, nullptr, h.csplit, m, h.m1f, b.m2f, b.argc, nullptr, nullptr, 0));
+    return launch_km_resolve(ctx, dx, n, nullptr, w.dc, m, d, h.xxs, b.ymax, h.prep, b.m2f, b.argc, w.label, b.ub, b.lb, nullptr, nullptr, w.colscale,
+                             nullptr, groups ? g.cperm.get() : nullptr);
+  }
+  // the part of a sweep after the assignment: new centres, their movement, the bounds, the list of open rows
+  int sweep_tail(const double* xl, bool groups, double scaled_tol) {
+    const int nwg = plan.nwg, S = plan.S;
+    MLN_HIP(ctx, hipMemsetAsync(w.shift, 0, sizeof(double), st));
+    hipLaunchKernelGGL(k_finish, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.dc, w.sums, w.counts, m, d, w.sq, b.delta, w.colscale);
+    hipLaunchKernelGGL(k_km_sum_fixed, dim3(1), dim3(256), 0, st, w.sq, m, w.shift, scaled_tol, b.kstate);
+    if (groups) {
+      hipLaunchKernelGGL(k_km_stage_delta, dim3((unsigned)S), dim3(256), 0, st, b.delta, g.cperm, m, g.cum);
+      hipLaunchKernelGGL(k_km_bounds_g, dim3((unsigned)nwg), dim3(256), 0, st, xl, n, d, w.dc, w.label, b.ub, g.lbg, g.cum, S, g.cposd, b.kstate,
+                         b.wg_count, b.flagged_tmp, g.rowmask);
+    } else {
+      hipLaunchKernelGGL(k_km_delta_stats, dim3(1), dim3(256), 0, st, b.delta, m, b.dstat);
+      hipLaunchKernelGGL(k_km_bounds, dim3((unsigned)nwg), dim3(256), 0, st, xl, n, d, w.dc, w.label, b.ub, b.lb, b.delta, b.dstat, b.kstate,
+                         b.wg_count, b.flagged_tmp);
+    }
+    hipLaunchKernelGGL(k_km_flag_scan, dim3(1), dim3(1024), 0, st, b.wg_count, nwg, b.wg_off, b.nflag);
+    hipLaunchKernelGGL(k_km_flag_compact, dim3((unsigned)nwg), dim3(256), 0, st, b.flagged_tmp, b.wg_count, b.wg_off, b.flagged);
+    return MLN_OK;
+  }
+  // ---- group-bound set-up, once per level.  The host buffers of n entries are locals, freed before the sweeps start; a
+  // function returns early only where none of its locals is still being copied.
+  int centre_order() {                       // the centres' sweep order (host) -> cperm, cposd
+    std::vector<double> hc((size_t)m * d);
+    g.h_order.resize((size_t)m); g.h_cpos.resize((size_t)m);
+    MLN_HIP(ctx, hipMemcpyAsync(hc.data(), w.dc, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToHost, st));
+    MLN_HIP(ctx, hipStreamSynchronize(st));
+    centre_sweep_order(hc.data(), (int)m, d, g.h_order.data());
+    for (int p = 0; p < (int)m; ++p) g.h_cpos[(size_t)g.h_order[p]] = p;
+    MLN_HIP(ctx, hipMemcpyAsync(g.cperm, g.h_order.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st));
+    MLN_HIP(ctx, hipMemcpyAsync(g.cposd, g.h_cpos.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st));
+    MLN_HIP(ctx, hipStreamSynchronize(st));
+    return MLN_OK;
+  }
+  // the cells (dxs) and their state sorted by the sweep position of their first label: a stable counting sort on the host, the
+  // same order from run to run
+  int sort_cells() {
+    std::vector<int> hl((size_t)n), hperm((size_t)n);
+    MLN_HIP(ctx, hipMemcpyAsync(hl.data(), w.label, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    MLN_HIP(ctx, hipStreamSynchronize(st));
+    std::vector<int64_t> start((size_t)m + 1, 0);
+    for (int64_t i = 0; i < n; ++i) start[(size_t)g.h_cpos[(size_t)hl[(size_t)i]] + 1]++;
+    for (int64_t p = 0; p < m; ++p) start[(size_t)p + 1] += start[(size_t)p];
+    for (int64_t i = 0; i < n; ++i) hperm[(size_t)start[(size_t)g.h_cpos[(size_t)hl[(size_t)i]]]++] = (int)i;
+    MLN_HIP(ctx, hipMemcpyAsync(g.perm, hperm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_km_gather_rows, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, st, dx, g.perm, n, d, g.dxs);
+    hipLaunchKernelGGL(k_km_gather_state, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g.perm, n, w.label, b.ub, b.lb, g.label_s, g.ub_s, g.lb_s);
+    MLN_HIP(ctx, hipStreamSynchronize(st));                // (hperm is the copy's source)
+    std::swap(w.label, g.label_s); std::swap(b.ub, g.ub_s); std::swap(b.lb, g.lb_s);
+    return MLN_OK;
+  }
+  // centre order, sweep 0 on the centres in that order, the sorted cells and their split, the stage minima of every cell, the
+  // first group bounds
+  int groups_setup(const KmGroups& grp) {
+    MLN_TRY(centre_order());
+    MLN_TRY(sweep0(true));
+    MLN_TRY(sort_cells());
+    MLN_TRY(launch_split_f16(ctx, g.dxs, n, d, h.xsplit, h.xxs, nullptr, 1, h.prep));      // the same rows, in the new order
+    MLN_TRY(launch_rowmin_masked(ctx, h.xsplit, n, nullptr, h.csplit, m, nullptr, nullptr, nullptr, nullptr, nullptr, 0, g.smin, n));
+    return launch_km_init_groups(ctx, n, w.label, b.lb, h.xxs, b.ymax, h.prep, &grp);
+  }
+  // Sweep 0, then the sweeps over the open rows, queued eight at a time: their number (nflag) and the stopping test (kstate) stay
+  // on the device -- a sweep behind the converged one finds no open row and moves nothing.
+  int lloyd_bounded(int max_iter, double scaled_tol, int* it) {
+    const bool groups = plan.prune;
+    const KmGroups grp{g.lbg, g.cum, g.smin, n, g.cposd, plan.S};
+    if (groups) MLN_TRY(groups_setup(grp));
+    else MLN_TRY(sweep0(false));
+    const double* xl = groups ? g.dxs.get() : dx;        // the cells in the order the sweeps walk them
+    MLN_HIP(ctx, hipMemsetAsync(w.sums, 0, sizeof(double) * (size_t)m * d, st));
+    MLN_HIP(ctx, hipMemsetAsync(w.counts, 0, sizeof(double) * (size_t)m, st));
+    hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n + 3) / 4)), dim3(64, 4), 0, st, xl, n, d, w.label, w.sums, w.counts, w.colscale);
+    MLN_TRY(sweep_tail(xl, groups, scaled_tol));
+    for (;;) {
+      int hk[2] = {0, 0};
+      MLN_HIP(ctx, hipMemcpyAsync(hk, b.kstate, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+      MLN_HIP(ctx, hipStreamSynchronize(st));
+      *it = hk[1];
+      if (hk[0] || *it >= max_iter) return MLN_OK;
+      const int batch = (max_iter - *it < 8) ? max_iter - *it : 8;
+      for (int k = 0; k < batch; ++k) {
+        MLN_TRY(centres_split(groups));
+        if (groups) hipLaunchKernelGGL(k_km_block_mask_g, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b.flagged, b.nflag, g.rowmask, g.smask);
+        const uint32_t* smask = groups ? g.smask.get() : nullptr;
+        MLN_TRY(launch_rowmin_masked(ctx, h.xsplit, n, b.nflag, h.csplit, m, h.m1f, b.m2f, b.argc, b.flagged, smask, groups ? 1 : 0,
+                                     groups ? g.smin.get() : nullptr, n));       // (winner and stage minima in one sweep)
+        MLN_TRY(launch_km_resolve(ctx, xl, n, b.flagged, w.dc, m, d, h.xxs, b.ymax, h.prep, b.m2f, b.argc, w.label, b.ub, b.lb, w.sums, w.counts,
+                                  w.colscale, b.nflag, groups ? g.cperm.get() : nullptr, groups ? &grp : nullptr, smask, 1));
+        MLN_TRY(sweep_tail(xl, groups, scaled_tol));
+      }
+    }
+  }
+  // sum of squared distances to the closest final centre: one exact assignment
+  int inertia(double* out) {
+    hipLaunchKernelGGL(k_sqnorm_rows, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.dc, m, d, w.cc);
+    assign_exact();
     std::vector<double> hm((size_t)n);
-    chk(hipMemcpyAsync(hm.data(), mind, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    chk(hipStreamSynchronize(st));
+    MLN_HIP(ctx, hipMemcpyAsync(hm.data(), w.mind, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    MLN_HIP(ctx, hipStreamSynchronize(st));
     double s = 0.0;
     for (double v : hm) s += v;
-    *inertia_out = s;
+    *out = s;
+    return MLN_OK;
   }
-  if (rc == MLN_OK) {
-    chk(hipGetLastError());
-    chk(hipMemcpyAsync(centers, dc, sizeof(double) * (size_t)m * d, hipMemcpyDefault, st));
-    chk(hipStreamSynchronize(st));
-  }
+};
+
+// One level: k-means++ seeding (or the centres in `init`, device, m x d) followed by Lloyd's iterations on the n cells at x.
+// `drain` is declared after the workspaces in L: on every way out the stream is idle before any of them is released.
+static int kmeans_level(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int64_t m, int64_t seed, int32_t max_iter, double tol,
+                        const double* init, double* centers, int32_t* n_iter_out, double* inertia_out) {
+  KmLevel L{ctx, ctx->stream, n, m, d, km_plan(n, d, m, init)};
+  DrainOnExit drain{ctx->stream};
+  MLN_TRY(L.w.alloc(ctx, L.plan, n, d, m));
+  MLN_TRY(L.h.alloc(ctx, L.plan, n, m));
+  MLN_TRY(L.input(x));
+  MLN_TRY(L.seed(seed, init));
+  double scaled_tol = 0.0;
+  MLN_TRY(L.tolerance(tol, &scaled_tol));
+  MLN_TRY(L.b.alloc(ctx, L.plan, n, m));          // (here, not above: they zero kstate and cum on the stream)
+  MLN_TRY(L.g.alloc(ctx, L.plan, n, d, m));
+  int it = 0;
+  if (L.plan.bounds && max_iter > 0) MLN_TRY(L.lloyd_bounded(max_iter, scaled_tol, &it));
+  else MLN_TRY(L.lloyd_plain(max_iter, scaled_tol, &it));
+  if (inertia_out) MLN_TRY(L.inertia(inertia_out));
+  MLN_HIP(ctx, hipGetLastError());
+  MLN_HIP(ctx, hipMemcpyAsync(centers, L.w.dc, sizeof(double) * (size_t)m * d, hipMemcpyDefault, ctx->stream));
+  MLN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (n_iter_out) *n_iter_out = it;
-  (void)hipStreamSynchronize(st);
-  return rc;
+  return MLN_OK;
 }
 
 // ---- sklearn-compatible k-means++ seeding (round 5) ---------------------------------------------------------------------
@@ -1343,40 +1374,27 @@ static int sklearn_seed(mln_ctx* ctx, const double* dx, int64_t n, int d, int64_
   const int64_t nblk = (n + SBLK - 1) / SBLK;
   DevBuf<double> closest, tmp, part, bsum, duni, cb;
   DevBuf<SkState> state;
-  int rc = MLN_OK;
-  auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MLN_OK) rc = mln_hip_fail(ctx, e, "kmeans (sklearn seeding)", __FILE__, __LINE__); };
-  rc = closest.alloc(ctx, (size_t)n, "closest");
-  if (rc == MLN_OK) rc = tmp.alloc(ctx, (size_t)n * (size_t)L, "tmp");
-  if (rc == MLN_OK) rc = part.alloc(ctx, (size_t)nblk * SK_LMAX, "part");
-  if (rc == MLN_OK) rc = bsum.alloc(ctx, (size_t)nblk, "bsum");
-  if (rc == MLN_OK) rc = duni.alloc(ctx, (size_t)std::max<int64_t>(1, (m - 1) * L), "duni");
-  if (rc == MLN_OK) rc = state.alloc(ctx, 1, "state");
-  if (rc == MLN_OK) rc = cb.alloc(ctx, SK_LMAX * 64, "cb");
-  if (rc == MLN_OK) {
-    chk(hipMemsetAsync(state, 0, sizeof(SkState), st));
-    if (m > 1) chk(hipMemcpyAsync(duni, uniforms, sizeof(double) * (size_t)((m - 1) * L), hipMemcpyDefault, st));
-    chk(hipMemcpyAsync(dc, dx + first_id * d, sizeof(double) * (size_t)d, hipMemcpyDeviceToDevice, st));
-    chk(hipMemcpyAsync(indices, &first_id, sizeof(int64_t), hipMemcpyHostToDevice, st));
-    chk(hipStreamSynchronize(st));                 // (first_id is a stack variable)
+  MLN_TRY(alloc_all(ctx, closest, (size_t)n, "closest", tmp, (size_t)n * (size_t)L, "tmp", part, (size_t)nblk * SK_LMAX, "part", bsum, (size_t)nblk, "bsum",
+                    duni, (size_t)std::max<int64_t>(1, (m - 1) * L), "duni", state, 1, "state", cb, SK_LMAX * 64, "cb"));
+  MLN_HIP(ctx, hipMemsetAsync(state, 0, sizeof(SkState), st));
+  if (m > 1) MLN_HIP(ctx, hipMemcpyAsync(duni, uniforms, sizeof(double) * (size_t)((m - 1) * L), hipMemcpyDefault, st));
+  MLN_HIP(ctx, hipMemcpyAsync(dc, dx + first_id * d, sizeof(double) * (size_t)d, hipMemcpyDeviceToDevice, st));
+  MLN_HIP(ctx, hipMemcpyAsync(indices, &first_id, sizeof(int64_t), hipMemcpyHostToDevice, st));
+  MLN_HIP(ctx, hipStreamSynchronize(st));                 // (first_id is a stack variable)
+  hipLaunchKernelGGL(k_sk_update, dim3((unsigned)nblk), dim3(256), 0, st, dx, n, d, L, closest, tmp, bsum, state, m > 1 ? duni : nullptr, cb, 1, first_id);
+  for (int64_t c = 1; c < m; ++c) {
+    hipLaunchKernelGGL(k_sk_candidates, dim3((unsigned)nblk), dim3(256), 0, st, dx, n, d, L, closest, tmp, part, state, cb, dc, indices, (int)c);
+    hipLaunchKernelGGL(k_sk_update, dim3((unsigned)nblk), dim3(256), 0, st, dx, n, d, L, closest, tmp, bsum, state,
+                       c + 1 < m ? duni + c * L : nullptr, cb, 0, (int64_t)0);
   }
-  if (rc == MLN_OK) {
-    hipLaunchKernelGGL(k_sk_update, dim3((unsigned)nblk), dim3(256), 0, st, dx, n, d, L, closest, tmp, bsum, state, m > 1 ? duni : nullptr, cb, 1, first_id);
-    for (int64_t c = 1; c < m; ++c) {
-      hipLaunchKernelGGL(k_sk_candidates, dim3((unsigned)nblk), dim3(256), 0, st, dx, n, d, L, closest, tmp, part, state, cb, dc, indices, (int)c);
-      hipLaunchKernelGGL(k_sk_update, dim3((unsigned)nblk), dim3(256), 0, st, dx, n, d, L, closest, tmp, bsum, state,
-                         c + 1 < m ? duni + c * L : nullptr, cb, 0, (int64_t)0);
-    }
-    chk(hipGetLastError());
-    chk(hipStreamSynchronize(st));
-  }
-  if (rc == MLN_OK) {
-    // a NaN / inf coordinate makes the potential non-finite, every target then fails its interval test and the seeding would
-    // silently pick last cells (with max_iter = 0 kmeans_level's own check never runs): refuse, like mln_kmeans
-    SkState h;
-    chk(hipMemcpy(&h, state, sizeof(SkState), hipMemcpyDeviceToHost));
-    if (rc == MLN_OK && !std::isfinite(h.pot)) { mln_set_error(ctx, "kmeans (sklearn seeding): x contains non-finite values"); rc = MLN_ERR_ARG; }
-  }
-  return rc;
+  MLN_HIP(ctx, hipGetLastError());
+  MLN_HIP(ctx, hipStreamSynchronize(st));
+  // a NaN / inf coordinate makes the potential non-finite, every target then fails its interval test and the seeding would
+  // silently pick last cells (with max_iter = 0 kmeans_level's own check never runs): refuse, like mln_kmeans
+  SkState h;
+  MLN_HIP(ctx, hipMemcpy(&h, state, sizeof(SkState), hipMemcpyDeviceToHost));
+  if (!std::isfinite(h.pot)) { mln_set_error(ctx, "kmeans (sklearn seeding): x contains non-finite values"); return MLN_ERR_ARG; }
+  return MLN_OK;
 }
 
 extern "C" int mln_kmeans_sklearn(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int64_t m, int64_t first_id,
@@ -1389,31 +1407,17 @@ extern "C" int mln_kmeans_sklearn(mln_ctx* ctx, const double* x, int64_t n, int3
   }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
   const double* dx = x;
-  DevBuf<double> owned;
-  {
-    hipPointerAttribute_t attr;
-    if (!(hipPointerGetAttributes(&attr, x) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))) {
-      (void)hipGetLastError();
-      MLN_TRY(owned.alloc(ctx, (size_t)n * d, "owned"));
-      const hipError_t ce = hipMemcpyAsync(owned, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, ctx->stream);
-      if (ce != hipSuccess) return mln_hip_fail(ctx, ce, "kmeans (sklearn seeding): upload", __FILE__, __LINE__);
-      dx = owned;
-    }
-  }
-  DevBuf<double> dc;
+  DevBuf<double> owned, dc;
   DevBuf<int64_t> dind;
-  int rc = dc.alloc(ctx, (size_t)m * d, "kmeans (sklearn seeding): centres");
-  if (rc == MLN_OK) rc = dind.alloc(ctx, (size_t)m, "kmeans (sklearn seeding): indices");
-  if (rc == MLN_OK) rc = sklearn_seed(ctx, dx, n, d, m, first_id, uniforms, n_local_trials, dc, dind);
-  if (rc == MLN_OK && indices_out && hipMemcpy(indices_out, dind, sizeof(int64_t) * (size_t)m, hipMemcpyDefault) != hipSuccess) rc = MLN_ERR_HIP;
+  MLN_TRY(cells_on_device(ctx, x, (size_t)n * d, owned, "owned", &dx));
+  MLN_TRY(alloc_all(ctx, dc, (size_t)m * d, "kmeans (sklearn seeding): centres", dind, (size_t)m, "kmeans (sklearn seeding): indices"));
+  MLN_TRY(sklearn_seed(ctx, dx, n, d, m, first_id, uniforms, n_local_trials, dc, dind));   // (ends with the stream drained)
+  if (indices_out && hipMemcpy(indices_out, dind, sizeof(int64_t) * (size_t)m, hipMemcpyDefault) != hipSuccess) return MLN_ERR_HIP;
   // Lloyd's sweeps from these centres over ALL cells, to sklearn's stopping rule (max_iter = 0: the seeding alone)
-  if (rc == MLN_OK && max_iter > 0) rc = kmeans_level(ctx, dx, n, d, m, 0, max_iter, tol, dc, centers, n_iter_out, inertia_out);
-  else if (rc == MLN_OK) {
-    if (hipMemcpy(centers, dc, sizeof(double) * (size_t)m * d, hipMemcpyDefault) != hipSuccess) rc = MLN_ERR_HIP;
-    if (n_iter_out) *n_iter_out = 0;
-  }
-  (void)hipStreamSynchronize(ctx->stream);
-  return rc;
+  if (max_iter > 0) return kmeans_level(ctx, dx, n, d, m, 0, max_iter, tol, dc, centers, n_iter_out, inertia_out);
+  if (hipMemcpy(centers, dc, sizeof(double) * (size_t)m * d, hipMemcpyDefault) != hipSuccess) return MLN_ERR_HIP;
+  if (n_iter_out) *n_iter_out = 0;
+  return MLN_OK;
 }
 
 // A few Lloyd sweeps from given centres (device, m x d): the coarse clustering of the pruned 1-NN search (rowmin_f16.hip), where
@@ -1434,31 +1438,25 @@ extern "C" int mln_kmeans(mln_ctx* ctx, const double* x, int64_t n, int32_t d, i
   if (!ctx || !x || !centers) return MLN_ERR_ARG;
   if (n < 1 || d < 1 || d > 64 || m < 1 || m > n) { mln_set_error(ctx, "kmeans: bad shape (need 1 <= m <= n, d <= 64)"); return MLN_ERR_SHAPE; }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
-  const bool two_level = n >= 64 * m && n >= 200000 && m >= 2 &&
-                         !(mln_experiment("MELLON_AMD_KM_LEVELS") && std::atoi(mln_experiment("MELLON_AMD_KM_LEVELS")) == 1);
+  const char* levels = mln_experiment("MELLON_AMD_KM_LEVELS");     // (1: a single level)
+  const bool two_level = n >= 64 * m && n >= 200000 && m >= 2 && !(levels && std::atoi(levels) == 1);
   if (!two_level) return kmeans_level(ctx, x, n, d, m, seed, max_iter, tol, nullptr, centers, n_iter_out, inertia_out);
   hipStream_t st = ctx->stream;
   // the cells on the device once, for both levels
   const double* dx = x;
-  StreamBuf<double> owned, xs, c0;   // used on st only, drained below
-  hipPointerAttribute_t attr;
-  if (!(hipPointerGetAttributes(&attr, x) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))) {
-    (void)hipGetLastError();
-    MLN_TRY(owned.alloc(ctx, (size_t)n * d, "owned"));
-    MLN_HIP(ctx, hipMemcpyAsync(owned, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, st));
-    dx = owned;
-  }
+  StreamBuf<double> owned, xs, c0;   // used on st only, which `drain` empties before they go
+  DrainOnExit drain{st};
+  MLN_TRY(cells_on_device(ctx, x, (size_t)n * d, owned, "owned", &dx));
   const int64_t want = std::max<int64_t>(32 * m, n / 8);
   const int64_t stride = std::max<int64_t>(1, n / want);
   const int64_t ns = (n + stride - 1) / stride;
-  int rc = xs.alloc(ctx, (size_t)ns * d, "xs");
-  if (rc == MLN_OK) rc = c0.alloc(ctx, (size_t)m * d, "c0");
-  if (rc == MLN_OK && hipMemcpy2DAsync(xs, sizeof(double) * d, dx, sizeof(double) * d * stride, sizeof(double) * d, (size_t)ns,
-                                       hipMemcpyDeviceToDevice, st) != hipSuccess) rc = MLN_ERR_HIP;
+  MLN_TRY(xs.alloc(ctx, (size_t)ns * d, "xs"));
+  MLN_TRY(c0.alloc(ctx, (size_t)m * d, "c0"));
+  if (hipMemcpy2DAsync(xs, sizeof(double) * d, dx, sizeof(double) * d * stride, sizeof(double) * d, (size_t)ns,
+                       hipMemcpyDeviceToDevice, st) != hipSuccess) return MLN_ERR_HIP;
   int32_t it0 = 0, it1 = 0;
-  if (rc == MLN_OK) rc = kmeans_level(ctx, xs, ns, d, m, seed, max_iter, tol, nullptr, c0, &it0, nullptr);
-  if (rc == MLN_OK) rc = kmeans_level(ctx, dx, n, d, m, seed, max_iter, tol, c0, centers, &it1, inertia_out);
+  MLN_TRY(kmeans_level(ctx, xs, ns, d, m, seed, max_iter, tol, nullptr, c0, &it0, nullptr));
+  MLN_TRY(kmeans_level(ctx, dx, n, d, m, seed, max_iter, tol, c0, centers, &it1, inertia_out));
   if (n_iter_out) *n_iter_out = it0 + it1;
-  (void)hipStreamSynchronize(st);
-  return rc;
+  return MLN_OK;
 }

@@ -7,6 +7,7 @@ int comm_allreduce(mln_ctx* ctx, double* dev, int64_t count);                   
 int comm_bcast0(mln_ctx* ctx, double* dev, int64_t count);                          // rank 0 -> all
 int comm_allgather(mln_ctx* ctx, const double* send, double* recv, int64_t count);  // count per rank, rank order
 void comm_release(mln_ctx* ctx);
+bool is_device_ptr(const void* p);   // api.hip: device or managed memory (a failed query is cleared and means host)
 
 // ---- kernel launchers (all asynchronous on ctx->stream; device pointers only) ---------------
 // cov_kernels.hip

@@ -23,3 +23,5 @@ inline const char* mln_experiment(const char* name) {
   static const bool on = [] { const char* e = std::getenv("MELLON_AMD_EXPERIMENTAL"); return e && std::atoi(e) != 0; }();
   return on ? std::getenv(name) : nullptr;
 }
+// an on-by-default path switched off: the knob is set and reads as 0
+inline bool mln_knob_off(const char* name) { const char* e = mln_experiment(name); return e && std::atoi(e) == 0; }

@@ -955,7 +955,7 @@ static int nn_search_core(mln_ctx* ctx, const double* x, int64_t n, const double
   if (fold && (!alloc((void**)&fthr, sizeof(float) * n) || !alloc((void**)&fdd, sizeof(double) * n))) {
     mln_set_error(ctx, "nn_distances: out of device memory"); return cleanup(MLN_ERR_HIP);
   }
-  const bool list_ok = !(mln_experiment("MELLON_AMD_NN_LIST") && std::atoi(mln_experiment("MELLON_AMD_NN_LIST")) == 0);
+  const bool list_ok = !mln_knob_off("MELLON_AMD_NN_LIST");
   // (Measured and taken out, round 5: a first sweep with the hi.hi product alone -- a third of the matrix work, values to
   //  2^-9 |x||y| instead of 2^-18.  At C3 it left 55 % of the rows open -- in 50 dimensions the gap to the second neighbour
   //  is a few per cent of |x||y| -- and took 249 ms against the three-product sweep's 360: its two-instruction epilogue is
@@ -1208,7 +1208,7 @@ int nn_distances_prefiltered(mln_ctx* ctx, const double* x, int64_t n, const dou
                              int64_t self_offset, double* out, double* stats) {
   // one set against itself, folded operands, enough cells for the clustering to pay: the pruned search
   // (MELLON_AMD_NN_PRUNE=0, experiment: every row block sweeps every candidate block)
-  const bool prune_ok = !(mln_experiment("MELLON_AMD_NN_PRUNE") && std::atoi(mln_experiment("MELLON_AMD_NN_PRUNE")) == 0);
+  const bool prune_ok = !mln_knob_off("MELLON_AMD_NN_PRUNE");
   if (prune_ok && x == y && n == m && self_offset == 0 && d <= KP - 3 && n >= (int64_t)1 << 18 && n <= (int64_t)1 << 25)
     return nn_distances_pruned(ctx, x, n, d, out, stats);
   return nn_search_core(ctx, x, n, y, m, d, self_offset, out, stats, nullptr);
