@@ -179,7 +179,11 @@ class Predictor:
 
     # -- leverage / observation variance (base_predictor.py:263-355) -------------------------------------------
     def leverage(self, x):
-        """Hat-matrix diagonal h_i used by the HC3 correction r^2 / (1 - h)^2."""
+        """Hat-matrix diagonal h_i used by the HC3 correction r^2 / (1 - h)^2.  A predictor fitted on cells sharded
+        across ranks: COLLECTIVE for the landmark conditionals -- the leverage is defined through B^T B, B = cov(x, x_u),
+        over the queried points, so x is this rank's shard of one global query set, every rank must call, and each
+        rank gets its rows.  (mean, gradient, hessian, covariance, mean_covariance, uncertainty, obs_variance and
+        to_json read replicated state only: any rank may call them alone.)"""
         x = self._check_features(x)
         if not hasattr(self, "_leverage"):
             raise NotImplementedError(f"{self.__class__.__name__} has no leverage.")
@@ -188,7 +192,8 @@ class Predictor:
         return self._leverage(x, self.sigma)
 
     def loo_residuals_squared(self, x, y):
-        """Squared leave-one-out residuals through the leverage shortcut (base_predictor.py:290-324)."""
+        """Squared leave-one-out residuals through the leverage shortcut (base_predictor.py:290-324).  Collective under
+        ranks, like `leverage`: x, y are this rank's shard of one global query set."""
         x = self._check_features(x)
         y = np.asarray(validate_array(y, "y"), dtype=np.float64)
         residual = y - self._mean(x)

@@ -94,12 +94,42 @@ def _full_leverage(x, cov_func, sigma, jitter):
     return 1.0 - s2 * (s - c) / (s * s), fit
 
 
+def _context_without_ranks(ctx):
+    """A device context on ctx's GPU that belongs to no communicator (made once per ctx): what runs on it sums over
+    nothing but its own rows."""
+    solo = getattr(ctx, "_solo", None)
+    if solo is None or solo.handle is None:
+        solo = ctx._solo = _lib.Context(ctx.device)
+    return solo
+
+
+def _kernel_gram_all_ranks(ctx, desc, Xnew, xu):
+    """B^T B, B = cov(Xnew, xu), over the queried points of ALL ranks (Xnew: this rank's shard of them).  Single rank:
+    ctx.kernel_gram itself.  Under ranks the queried points are gathered over the host communicator (n x d, as the cells
+    are for the nn distances and the landmarks) and EVERY rank forms the Gram of all of them with the single-rank call
+    on a context without communicator: the sum then runs in the single-rank order and gives the single-rank bits.
+    An all-reduce of per-rank Grams is the cheaper sum and not good enough: the leverage inverts
+    M = sigma^2 K_uu + B^T B + jitter I, whose condition number reaches 1e11, so re-associating B^T B alone moves the
+    leverage by 1e-8 of its size -- and mln_kernel_gram all-reduces once per 65536-row chunk, so
+    shards that span different numbers of chunks would not even make the same number of collective calls.  The price
+    is the n m^2 work of this one step on every rank instead of 1 / world_size of it; rows are still streamed in
+    chunks, so nothing n x m is held.  The block route keeps its one all-reduce of K^T K."""
+    from .distributed import current
+    comm = current()
+    if comm.world_size == 1 or isinstance(desc, _lib.BlockEvaluatedCov):
+        return ctx.kernel_gram(desc, Xnew, xu)
+    Xh = Xnew.to_host() if isinstance(Xnew, _lib.DeviceArray) else np.ascontiguousarray(ensure_2d(Xnew), dtype=np.float64)
+    X_all = np.ascontiguousarray(np.concatenate(comm.host.allgather(Xh), axis=0))
+    return _context_without_ranks(ctx).kernel_gram(desc, X_all, xu)
+
+
 def _landmarks_leverage(Xnew, xu, cov_func, sigma, jitter, L=None):
     """diag(B M^-1 B^T), B = cov(Xnew, xu), M = sigma^2 K_uu + B^T B + jitter I (conditional.py:660-685);
-    K_uu = L L^T when the predictor carries L, cov(xu, xu) otherwise -- as in the reference."""
+    K_uu = L L^T when the predictor carries L, cov(xu, xu) otherwise -- as in the reference.  Under ranks B^T B is
+    over the queried points of all ranks (a collective call), the result this rank's rows."""
     ctx = _lib.default_context()
     desc = cov_func.lower(xu.shape[1])
-    S = ctx.kernel_gram(desc, Xnew, xu)
+    S = _kernel_gram_all_ranks(ctx, desc, Xnew, xu)
     K_uu = (np.asarray(L) @ np.asarray(L).T) if L is not None else ctx.kernel_matrix(desc, xu, xu)
     M = float(sigma) ** 2 * K_uu + S
     Lm = ctx.chol_lower(M, add_diag=jitter, jitter=jitter)
@@ -137,7 +167,7 @@ def _landmarks_leverage_any(Xnew, xu, cov_func, sigma, jitter, L=None):
         for k, (_, cols) in enumerate(levels):
             h[:, cols] = per_level[:, k:k + 1]
         return h
-    S = ctx.kernel_gram(desc, Xnew, xu)
+    S = _kernel_gram_all_ranks(ctx, desc, Xnew, xu)
     K_uu = (np.asarray(L) @ np.asarray(L).T) if L is not None else ctx.kernel_matrix(desc, xu, xu)
     kdiag = cov_func.diag(Xnew)
     h = np.empty((Xnew.shape[0], sig.shape[0]))
@@ -361,6 +391,23 @@ class _FullConditional:
 
 
 class _LandmarksConditional:
+    """Cells sharded over ranks (x, y -- dense or CSR rows --, a per-cell sigma, `y_cov_factor`: this rank's rows).
+    Which device calls sum over the ranks:
+
+      sparse_solve / sparse_solve_noise / sparse_solve_csr   A A^T (fit_gram) and A (y - mu) all-reduced; the m x m
+                                                             factor work and the weights replicated
+      the block route (_sparse_solve_blocks, kernel_gram)    K^T K and K^T (y - mu) all-reduced once each
+      kernel_gram (through _kernel_gram_all_ranks)           B^T B over the queried points of all ranks: a HOST gather
+                                                             of the points, then the single-rank Gram on every rank
+      landmark_leverage                                      L^T L all-reduced (fit_gram); the rows of h local
+      kernel_matrix(xu, xu), chol_lower, trsm_lower,         replicated inputs, no collective: Lp = chol(K_uu), Lm,
+      predict_mean, predict_covariance                       and per-row results for this rank's rows
+
+    So the weights, `L`, `Cs`, `W` and `variance_weights` are the same bits on every rank; `_corrected_r2` (the HC3
+    residuals: local rows, local leverage rows from the global B^T B) is this rank's rows, and the second solve on it
+    is all-reduced like the first.  With `y_is_mean` / `with_uncertainty`, y_cov_factor = L diag(std) is n_local x m
+    and enters through the same all-reduced A (.) product.  `n_obs` is the local count here; FunctionEstimator
+    replaces it by the global one."""
     _center_name = "landmarks"
 
     def _leverage(self, Xnew, sigma):
