@@ -562,6 +562,18 @@ int mln_diag_gram_i8(mln_ctx* ctx, const double* A, int64_t rows, int64_t m, dou
 /* ms of: kernel-matrix pass alone, Gram GEMM alone, both on two streams, Cholesky alone, kernel matrix ||
  * Cholesky, kernel matrix || (Cholesky then Gram) -- the measurement behind the two-stream set-up phase. */
 int mln_diag_overlap(mln_ctx* ctx, int64_t n, int64_t m, int32_t d, int64_t gram_rows, double* out /* 6 */);
+/* The fp16-split row-minimum sweep for cells with 65 to 256 features (csrc/rowmin_wide.hip) in isolation: x (n x d) against
+ * y (m x d), host or device, the pair (i, i + self_offset) skipped when exclude_self != 0.  Everything lives in the centred,
+ * scaled units x' = (x - centre) * scale that prep describes: m1[i] / m2[i] the smallest and second-smallest approximate
+ * value of s_ij = |y'_j|^2 - 2 x'_i . y'_j over j, arg[i] the column of the smallest, E[i] the bound on |approximate - exact|
+ * that the certification of the exact 1-NN search allows row i.  Requires 65 <= d <= 256.        */
+int mln_diag_rowmin_wide(mln_ctx* ctx, const double* x, int64_t n, const double* y, int64_t m, int32_t d,
+                         int64_t self_offset, int32_t exclude_self, float* m1, float* m2, int32_t* arg, double* E,
+                         double* prep /* d + 2: centre, scale, max centred squared norm */);
+/* What this context's last mln_nn_distances did: out[0] the route (0 scalar exact, 1 fp64 matrix-core exact, 2 pre-filter
+ * d <= 64, 3 pruned, 4 wide: 65 <= d <= 256), out[1] rows the certification left open, out[2] rows resolved by the exact
+ * re-search, out[3] unused (0).                                                                  */
+int mln_diag_nn_last(mln_ctx* ctx, double* out /* 4 */);
 /* One launch of the fp64 objective kernel over `count` rows of the fit's buffer: first + i * stride (rows == NULL), or
  * rows[i] with optional per-row weights on the likelihood term.  Host pointers.  loss: the likelihood sum (times out_scale
  * when that is non-zero), grad (m): the rows' part of the gradient, f_rows (count): f of the rows in launch order; no prior. */

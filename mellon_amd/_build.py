@@ -15,14 +15,15 @@ SOURCES = ["api.hip", "api_fit.hip", "api_precond.hip", "api_solve.hip", "api_no
            "predict_rows_ratquad.hip", "predict_rows_prod_matern32.hip", "predict_rows_prod_matern52.hip",
            "predict_rows_prod_expquad.hip", "predict_rows_prod_exponential.hip", "kernel_rows_prod_matern32.hip", "kernel_rows_prod_matern52.hip",
            "kernel_rows_prod_expquad.hip", "kernel_rows_prod_exponential.hip",
-           "dgemm.hip", "diag.hip", "precond_rebuild.hip", "rowmin_f16.hip", "rowmin_w64.hip", "gram_i8.hip", "eigh.hip", "kmeans.hip", "linalg.hip", "potrf.hip", "objective.hip", "objective_batch.hip", "solver.hip", "tridiag.hip", "ldl_inertia.hip", "dimensionality.hip", "dim_objective_batch.hip", "slogdet.hip",
+           "dgemm.hip", "diag.hip", "precond_rebuild.hip", "rowmin_f16.hip", "rowmin_w64.hip", "rowmin_wide.hip", "gram_i8.hip", "eigh.hip", "kmeans.hip", "linalg.hip", "potrf.hip", "objective.hip", "objective_batch.hip", "solver.hip", "tridiag.hip", "ldl_inertia.hip", "dimensionality.hip", "dim_objective_batch.hip", "slogdet.hip",
            "predict_variance.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + (["-DMLN_POTRF_TIMING"] if __import__("os").environ.get("MLN_POTRF_TIMING") else [])
 
 
 # per-source extras: the one-wave-per-SIMD row-minimum sweep keeps its MFMA accumulators in architectural VGPRs (its vector
 # epilogue reads them directly; in AGPRs every element costs a v_accvgpr_read)
-EXTRA_FLAGS = {"rowmin_w64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# (the wide sweep, one wave per SIMD as well: 128 accumulators beside 32 c operand registers -- without the flag it goes to scratch)
+EXTRA_FLAGS = {"rowmin_w64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "rowmin_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 # the persistent-row kernel families take minutes each (the product kernels the longest): they start first, and the
 # short sources fill the workers around them, instead of a slow source starting last and setting the build's wall time

@@ -159,6 +159,8 @@ SYMBOLS = [
     ("mln_stage_times", C.c_int, [_vp, _dp]),
     ("mln_diag_peak", C.c_int, [_vp, _i32, _i64, C.POINTER(_dbl)]),
     ("mln_diag_overlap", C.c_int, [_vp, _i64, _i64, _i32, _i64, _dp]),
+    ("mln_diag_rowmin_wide", C.c_int, [_vp, _dp, _i64, _dp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _dp, _dp]),
+    ("mln_diag_nn_last", C.c_int, [_vp, _dp]),
     ("mln_diag_objective_rows", C.c_int, [_vp, _dp, _i64, _i64, _i64, _vp, _dp, _dbl, C.POINTER(_dbl), _dp, _dp]),
     ("mln_diag_gram_i8", C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, C.POINTER(_dbl)]),
     ("mln_diag_dgemm", C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _i32, C.POINTER(_dbl)]),
@@ -937,6 +939,30 @@ class Context:
         out = np.zeros(6)
         self._check(self.lib.mln_diag_overlap(self.handle, int(n), int(m), int(d), int(gram_rows), out.ctypes.data))
         return dict(zip(["k_ms", "gram_ms", "k_par_gram_ms", "chol_ms", "k_par_chol_ms", "k_par_chol_gram_ms"], out))
+
+    def diag_rowmin_wide(self, x, y=None, self_offset=0, exclude_self=False):
+        """The wide fp16-split row-minimum sweep (65 <= d <= 256) in isolation: (m1, m2, arg, E, prep) -- per row of x the
+        smallest and second-smallest approximate value of |y'_j|^2 - 2 x'_i . y'_j over the rows of y (default: x itself),
+        the column of the smallest, the bound the certification allows the row, and prep = (centre[d], scale, largest
+        centred squared norm) of the units x' = (x - centre) * scale all of them live in."""
+        x = _as2d(x)
+        y = x if y is None else _as2d(y)
+        if x.shape[1] != y.shape[1]:
+            raise ValueError(f"x has {x.shape[1]} features, y has {y.shape[1]}")
+        n, d = x.shape
+        m1, m2 = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.float32)
+        arg, E, prep = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64), np.empty(d + 2, dtype=np.float64)
+        self._check(self.lib.mln_diag_rowmin_wide(self.handle, _ptr(x), n, _ptr(y), y.shape[0], d, int(self_offset),
+                                                  int(bool(exclude_self)), m1.ctypes.data, m2.ctypes.data, arg.ctypes.data,
+                                                  E.ctypes.data, prep.ctypes.data))
+        return m1, m2, arg, E, prep
+
+    def nn_last(self):
+        """What this context's last nn_distances did: [route, rows the certification left open, rows resolved by the exact
+        re-search, 0]; route 0 scalar exact, 1 fp64 matrix-core exact, 2 pre-filter (d <= 64), 3 pruned, 4 wide (65..256)."""
+        out = np.zeros(4)
+        self._check(self.lib.mln_diag_nn_last(self.handle, out.ctypes.data))
+        return out
 
     def diag_gram_i8(self, a, reps=1):
         """(Gram of round(a * 8355711) / 8355711**2, ms per call): the preconditioner's integer Gram in isolation."""

@@ -11,6 +11,7 @@
 
 #include "mln_internal.h"
 #include "rowmin_f16.h"
+#include "rowmin_wide.h"
 #include "cov_tile.h"
 #include "cov_rows.h"
 #include "mln_options.h"
@@ -625,8 +626,13 @@ int launch_nn_distances(mln_ctx* ctx, const double* x, int64_t n, const double* 
   const char* e_min = std::getenv("MELLON_AMD_NN_PREFILTER_MIN");
   const bool prefilter = !(e_on && std::atoi(e_on) == 0);
   const int64_t min_pairs = e_min ? std::atoll(e_min) : ((int64_t)1 << 26);
+  // what this call did, for mln_diag_nn_last: the pre-filter routes fill it in themselves (2, 3, 4 and their open rows)
+  ctx->nn_last[0] = (d <= 64 && n * m >= 4096) ? 1.0 : 0.0;
+  ctx->nn_last[1] = ctx->nn_last[2] = ctx->nn_last[3] = 0.0;
   if (prefilter && d <= 64 && m >= 2 && n * m >= min_pairs && m < 2147483647LL)
     return nn_distances_prefiltered(ctx, x, n, y, m, d, self_offset, out, nullptr);
+  if (prefilter && d <= ROWMIN_WIDE_MAX_D && m >= 2 && n * m >= min_pairs && m < 2147483647LL && n < 2147483647LL)      // (65 <= d: rowmin_wide.hip)
+    return nn_distances_wide(ctx, x, n, y, m, d, self_offset, out);
   return launch_nn_distances_exact(ctx, x, n, y, m, d, self_offset, nullptr, out);
 }
 

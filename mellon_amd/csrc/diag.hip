@@ -364,3 +364,65 @@ extern "C" int mln_diag_overlap(mln_ctx* ctx, int64_t n, int64_t m, int32_t d, i
   (void)hipStreamDestroy(side.stream);
   return MLN_OK;
 }
+
+// ---- the wide row-minimum sweep (rowmin_wide.hip) in isolation, and what the last nearest-neighbour search did ----------
+#include "rowmin_f16.h"
+#include "rowmin_wide.h"
+// The sweep's raw outputs for x (n x d) against y (m x d), host or device, 65 <= d <= 256: m1 / m2 / arg per query row, E the
+// bound the certification allows that row, prep (d + 2) the centre, scale and largest centred squared norm of the units all
+// of them live in.
+extern "C" int mln_diag_rowmin_wide(mln_ctx* ctx, const double* x, int64_t n, const double* y, int64_t m, int32_t d,
+                                    int64_t self_offset, int32_t exclude_self, float* m1, float* m2, int32_t* arg, double* E,
+                                    double* prep) {
+  if (!ctx || !x || !y || !m1 || !m2 || !arg || !E || !prep) return MLN_ERR_ARG;
+  if (n < 1 || m < 1 || m > 2147483647LL || d <= 64 || d > ROWMIN_WIDE_MAX_D) {
+    mln_set_error(ctx, "diag_rowmin_wide: bad shape (need n, m >= 1 and 65 <= d <= 256)");
+    return MLN_ERR_SHAPE;
+  }
+  MLN_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const bool same = (x == y && n == m);
+  StreamBuf<double> dx, dy, xx, yy, ymax, dE, dprep;      // used on st only, drained before they go
+  StreamBuf<char> xs, ys;
+  StreamBuf<float> yyf, dm1, dm2;
+  StreamBuf<int> darg;
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+  const size_t np = rowmin_wide_prep_doubles(d);
+  MLN_TRY(dx.alloc(ctx, (size_t)n * d, "x"));
+  if (!same) MLN_TRY(dy.alloc(ctx, (size_t)m * d, "y"));
+  MLN_TRY(xx.alloc(ctx, (size_t)n, "xx"));
+  MLN_TRY(yy.alloc(ctx, (size_t)m, "yy"));
+  MLN_TRY(ymax.alloc(ctx, 1, "ymax"));
+  MLN_TRY(dE.alloc(ctx, (size_t)n, "E"));
+  MLN_TRY(dprep.alloc(ctx, np, "prep"));
+  MLN_TRY(xs.alloc(ctx, rowmin_wide_split_bytes(n, d), "xs"));
+  MLN_TRY(ys.alloc(ctx, rowmin_wide_split_bytes(m, d), "ys"));
+  MLN_TRY(yyf.alloc(ctx, (size_t)m, "yyf"));
+  MLN_TRY(dm1.alloc(ctx, (size_t)n, "m1"));
+  MLN_TRY(dm2.alloc(ctx, (size_t)n, "m2"));
+  MLN_TRY(darg.alloc(ctx, (size_t)n, "arg"));
+  MLN_HIP(ctx, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)n * d, hipMemcpyDefault, st));
+  if (!same) MLN_HIP(ctx, hipMemcpyAsync(dy, y, sizeof(double) * (size_t)m * d, hipMemcpyDefault, st));
+  const double* cy = same ? dx.get() : dy.get();
+  MLN_TRY(rowmin_wide_prepare(ctx, cy, m, same ? nullptr : dx.get(), n, d, dprep));
+  MLN_TRY(launch_split_wide(ctx, dx, n, d, xs, xx, nullptr, 1, dprep));
+  MLN_TRY(launch_split_wide(ctx, cy, m, d, ys, yy, yyf, 2, dprep));
+  MLN_TRY(launch_max_norm(ctx, yy, m, ymax));
+  MLN_TRY(launch_rowmin_wide(ctx, xs, n, ys, m, d, yyf, self_offset, exclude_self ? 1 : 0, dm1, dm2, darg));
+  MLN_TRY(launch_rowmin_wide_bound(ctx, xx, n, ymax, d, dE));
+  MLN_HIP(ctx, hipMemcpyAsync(m1, dm1, sizeof(float) * (size_t)n, hipMemcpyDefault, st));
+  MLN_HIP(ctx, hipMemcpyAsync(m2, dm2, sizeof(float) * (size_t)n, hipMemcpyDefault, st));
+  MLN_HIP(ctx, hipMemcpyAsync(arg, darg, sizeof(int) * (size_t)n, hipMemcpyDefault, st));
+  MLN_HIP(ctx, hipMemcpyAsync(E, dE, sizeof(double) * (size_t)n, hipMemcpyDefault, st));
+  MLN_HIP(ctx, hipMemcpyAsync(prep, dprep, sizeof(double) * np, hipMemcpyDefault, st));
+  MLN_HIP(ctx, hipStreamSynchronize(st));
+  return MLN_OK;
+}
+
+// out[0] route of this context's last mln_nn_distances (0 scalar exact, 1 fp64 matrix-core exact, 2 pre-filter d <= 64,
+// 3 pruned, 4 wide), out[1] rows the certification left open, out[2] rows resolved by the exact re-search, out[3] spare
+extern "C" int mln_diag_nn_last(mln_ctx* ctx, double* out) {
+  if (!ctx || !out) return MLN_ERR_ARG;
+  for (int k = 0; k < 4; ++k) out[k] = ctx->nn_last[k];
+  return MLN_OK;
+}

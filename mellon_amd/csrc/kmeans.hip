@@ -13,7 +13,8 @@
 //   Lloyd     stops when the summed squared centre shift <= tol * mean feature variance (sklearn's rule) or after max_iter sweeps;
 //             update, stopping test and final inertia are fp64 on every path.  km_plan picks one of three drivers:
 //     plain     every sweep assigns every cell -- fp64 tiles with a running arg-min (k_assign / k_assign_mfma) or, from 2^24 pairs
-//               on, the fp16-split product (rowmin_f16.hip; MELLON_AMD_KM_FP16=0 disables) -- and downloads the shift
+//               on, the fp16-split product (rowmin_f16.hip, for 65 <= d <= 256 rowmin_wide.hip; MELLON_AMD_KM_FP16=0 disables)
+//               -- and downloads the shift; the only driver for d > 64 (fp64 seeding, no bounds)
 //     Hamerly   with the folded fp16 product (2^24 pairs, d <= 61): an upper and ONE lower bound per cell; sweep 0 searches every
 //               cell, later sweeps those whose bounds no longer decide; the stopping test stays on the device (_KM_BOUNDS=0: plain)
 //     groups    and m in [1024, 8192], n >= 65536: a lower bound per 256-centre stage, centres ordered by bisection, cells sorted
@@ -27,6 +28,7 @@
 #include "mln_internal.h"
 
 #include "rowmin_f16.h"
+#include "rowmin_wide.h"
 #include "mln_options.h"
 
 namespace {
@@ -44,7 +46,7 @@ __global__ void k_sqnorm_rows(const double* __restrict__ x, int64_t n, int d, do
 __global__ __launch_bounds__(256) void k_seed_update(const double* __restrict__ x, int64_t n, int d,
                                                      const double* __restrict__ c, double* __restrict__ mind,
                                                      double* __restrict__ bsum, int first) {
-  __shared__ double cs[64];
+  __shared__ double cs[ROWMIN_WIDE_MAX_D];     // (the centre: any d the ABI accepts)
   __shared__ double red[256];
   for (int k = threadIdx.x; k < d; k += 256) cs[k] = c[k];
   __syncthreads();
@@ -796,7 +798,9 @@ struct KmPlan {
   // seeded: k-means++ draws (no `init`); prepared: the half-precision copies apply (prep and xxs are made); fold: |c|^2 travels
   // inside the fp16 operands (d <= 61); seed_h: the seeding reads the fp16 cells; fast_assign: the assignment runs on the matrix
   // cores; bounds / prune: the sweeps carry Hamerly bounds / group bounds on sorted cells (acted on when max_iter > 0)
-  bool seeded, prepared, fold, seed_h, fast_assign, bounds, prune;
+  // wide: 65 <= d <= 256 -- the assignment runs on the matrix cores through the chunked sweep (rowmin_wide.hip), plain Lloyd
+  // only: no bounds, no half-precision seeding
+  bool seeded, prepared, fold, seed_h, fast_assign, bounds, prune, wide;
   int S, nwg;             // 256-centre stages of a sweep; workgroups of the bound kernels
   int64_t nblk, nblk_h;   // block sums of the fp64 / the half-precision seeding
 };
@@ -808,6 +812,7 @@ static KmPlan km_plan(int64_t n, int d, int64_t m, const double* init) {
   p.fold = d <= 61;
   p.seed_h = fp16 && p.prepared && p.fold;
   p.fast_assign = fp16 && p.prepared;
+  p.wide = fp16 && d > 64 && d <= ROWMIN_WIDE_MAX_D && n * m >= ((int64_t)1 << 24) && m >= 2;
   // (the bounds' error term needs xxs: `prepared`, which fast_assign implies -- a failed allocation ends the level before)
   p.bounds = p.fast_assign && p.fold && !mln_knob_off("MELLON_AMD_KM_BOUNDS");
   p.S = (int)((m + 255) / 256);
@@ -843,7 +848,10 @@ struct KmHalf {                              // operands of the fp16 matrix core
   StreamBuf<double> prep, xxs;               // centre and scale of the copies (rowmin_prepare); |x|^2 of the centred, scaled cells
   StreamBuf<char> xsplit, csplit;
   StreamBuf<float> ccf, m1f;
-  int alloc(mln_ctx* ctx, const KmPlan& p, size_t n, size_t m) {
+  int alloc(mln_ctx* ctx, const KmPlan& p, size_t n, size_t d, size_t m) {
+    if (p.wide)
+      return alloc_all(ctx, prep, rowmin_wide_prep_doubles((int)d), "prep", xsplit, rowmin_wide_split_bytes((int64_t)n, (int)d), "xsplit",
+                       csplit, rowmin_wide_split_bytes((int64_t)m, (int)d), "csplit", ccf, m, "ccf", m1f, n, "m1f");
     if (p.prepared) MLN_TRY(alloc_all(ctx, prep, ROWMIN_PREP_DOUBLES, "prep", xxs, n, "xxs"));
     if (!p.fast_assign) return MLN_OK;
     return alloc_all(ctx, xsplit, rowmin_split_bytes(n), "xsplit", csplit, rowmin_split_bytes(m), "csplit", ccf, m, "ccf", m1f, n, "m1f");
@@ -912,6 +920,7 @@ struct KmLevel {                             // one level's state and its stages
     int64_t cur = (int64_t)(rng.uniform() * (double)n);
     if (cur >= n) cur = n - 1;
     if (plan.prepared) MLN_TRY(rowmin_prepare(ctx, dx, n, nullptr, 0, d, h.prep));
+    if (plan.wide) MLN_TRY(rowmin_wide_prepare(ctx, dx, n, nullptr, 0, d, h.prep));
     if (plan.seed_h) MLN_TRY(launch_split_f16(ctx, dx, n, d, h.xsplit, h.xxs, nullptr, 1, h.prep));
     if (!plan.seeded) MLN_HIP(ctx, hipMemcpyAsync(dc, init, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToDevice, st));
     else MLN_HIP(ctx, hipMemcpyAsync(dc, dx + cur * d, sizeof(double) * d, hipMemcpyDeviceToDevice, st));
@@ -942,6 +951,7 @@ struct KmLevel {                             // one level's state and its stages
     *scaled_tol = tol * var_sum / d;
     hipLaunchKernelGGL(k_sqnorm_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx, n, d, w.xx);
     if (plan.fast_assign && !plan.seed_h) MLN_TRY(launch_split_f16(ctx, dx, n, d, h.xsplit, h.xxs, nullptr, plan.fold ? 1 : 0, h.prep));
+    if (plan.wide) MLN_TRY(launch_split_wide(ctx, dx, n, d, h.xsplit, nullptr, nullptr, 1, h.prep));      // the cells, once per level
     return MLN_OK;
   }
   // the exact fp64 assignment of every cell (label, squared distance in mind) to the centres whose |c|^2 is in cc
@@ -960,6 +970,9 @@ struct KmLevel {                             // one level's state and its stages
       if (plan.fast_assign) {
         MLN_TRY(launch_split_f16(ctx, w.dc, m, d, h.csplit, nullptr, h.ccf, 2 * fold, h.prep));
         MLN_TRY(launch_rowmin_f16x3(ctx, h.xsplit, n, h.csplit, m, h.ccf, 0, 0, h.m1f, nullptr, w.label, fold));
+      } else if (plan.wide) {
+        MLN_TRY(launch_split_wide(ctx, w.dc, m, d, h.csplit, nullptr, h.ccf, 2, h.prep));
+        MLN_TRY(launch_rowmin_wide(ctx, h.xsplit, n, h.csplit, m, d, h.ccf, 0, 0, h.m1f, nullptr, w.label));
       } else
         assign_exact();
       MLN_HIP(ctx, hipMemsetAsync(w.sums, 0, sizeof(double) * (size_t)m * d, st));
@@ -1102,7 +1115,7 @@ static int kmeans_level(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int
   KmLevel L{ctx, ctx->stream, n, m, d, km_plan(n, d, m, init)};
   DrainOnExit drain{ctx->stream};
   MLN_TRY(L.w.alloc(ctx, L.plan, n, d, m));
-  MLN_TRY(L.h.alloc(ctx, L.plan, n, m));
+  MLN_TRY(L.h.alloc(ctx, L.plan, n, d, m));
   MLN_TRY(L.input(x));
   MLN_TRY(L.seed(seed, init));
   double scaled_tol = 0.0;
@@ -1436,7 +1449,7 @@ int kmeans_lloyd_from(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int64
 extern "C" int mln_kmeans(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int64_t m, int64_t seed,
                           int32_t max_iter, double tol, double* centers, int32_t* n_iter_out, double* inertia_out) {
   if (!ctx || !x || !centers) return MLN_ERR_ARG;
-  if (n < 1 || d < 1 || d > 64 || m < 1 || m > n) { mln_set_error(ctx, "kmeans: bad shape (need 1 <= m <= n, d <= 64)"); return MLN_ERR_SHAPE; }
+  if (n < 1 || d < 1 || d > ROWMIN_WIDE_MAX_D || m < 1 || m > n) { mln_set_error(ctx, "kmeans: bad shape (need 1 <= m <= n, d <= 256)"); return MLN_ERR_SHAPE; }
   MLN_HIP(ctx, hipSetDevice(ctx->device));
   const char* levels = mln_experiment("MELLON_AMD_KM_LEVELS");     // (1: a single level)
   const bool two_level = n >= 64 * m && n >= 200000 && m >= 2 && !(levels && std::atoi(levels) == 1);

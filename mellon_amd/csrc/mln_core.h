@@ -43,6 +43,9 @@ struct mln_ctx {
   DevBuf<char> scratch;
   size_t scratch_bytes = 0;
   DevBuf<int> d_info;  // device int[4] for factorisation status
+  // what the last mln_nn_distances of this context did (mln_diag_nn_last): [0] route, [1] rows the certification left open,
+  // [2] rows the exact re-search resolved, [3] spare
+  double nn_last[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 template <class T, class Release>

@@ -25,6 +25,7 @@
 #include "mln_internal.h"
 
 #include "rowmin_f16.h"
+#include "rowmin_wide.h"
 // rowmin_w64.hip: the folded sweep, one wave per SIMD (round 6)
 int launch_rowmin_w64(mln_ctx* ctx, const _Float16* X, int64_t n, const _Float16* Y, int64_t m, int64_t self_offset, int exclude_self,
                       float* m1, float* m2, int* arg, const int* row_idx, const uint32_t* stage_mask, int mask_words, const int* wg_order,
@@ -1137,7 +1138,77 @@ static int nn_search_core(mln_ctx* ctx, const double* x, int64_t n, const double
     hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, og, open_rows, cnt, out);
   }
   if (hipGetLastError() != hipSuccess) return cleanup(MLN_ERR_HIP);
+  // what mln_diag_nn_last reports (host bookkeeping only)
+  ctx->nn_last[0] = prune ? 3.0 : 2.0;
+  ctx->nn_last[1] = (double)cnt;
+  ctx->nn_last[2] = (cnt > 0 && !listed) ? (double)cnt : 0.0;
   return cleanup(MLN_OK);
+}
+
+// The same search for 65 <= d <= 256 (rowmin_wide.hip): wide prepare, split and sweep, certification against the winner's exact
+// fp64 value in the same centred, scaled units, and the open rows through the exact fp64 search.  Queries and candidates are
+// always two split copies (the query rows carry -2 x).  No cluster pruning and no candidate-list second sweep.
+static int nn_search_wide(mln_ctx* ctx, const double* x, int64_t n, const double* y, int64_t m, int d,
+                          int64_t self_offset, double* out) {
+  const bool same = (x == y && n == m);
+  void *xs = nullptr, *ys = nullptr;
+  double *xx = nullptr, *yy = nullptr, *ymax = nullptr, *prep = nullptr;
+  float *yyf = nullptr, *m1 = nullptr, *m2 = nullptr;
+  int *arg = nullptr, *nflag = nullptr, *flagged = nullptr;
+  std::vector<StreamBuf<char>> owned;   // used on ctx->stream only, which cleanup drains
+  auto alloc = [&](void** p, size_t bytes) -> bool {
+    owned.emplace_back();
+    if (owned.back().alloc(ctx, bytes > 0 ? bytes : 8, "1-NN search workspace") != MLN_OK) return false;
+    *p = owned.back().get();
+    return true;
+  };
+  auto cleanup = [&](int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    owned.clear();
+    return rc;
+  };
+  bool ok = alloc(&xs, rowmin_wide_split_bytes(n, d)) && alloc(&ys, rowmin_wide_split_bytes(m, d)) &&
+            alloc((void**)&xx, sizeof(double) * n) && alloc((void**)&m1, sizeof(float) * n) && alloc((void**)&m2, sizeof(float) * n) &&
+            alloc((void**)&arg, sizeof(int) * n) && alloc((void**)&nflag, sizeof(int)) && alloc((void**)&flagged, sizeof(int) * n) &&
+            alloc((void**)&ymax, sizeof(double)) && alloc((void**)&yyf, sizeof(float) * m) &&
+            alloc((void**)&prep, sizeof(double) * rowmin_wide_prep_doubles(d));
+  if (ok && !same) ok = alloc((void**)&yy, sizeof(double) * m);
+  if (!ok) { mln_set_error(ctx, "nn_distances: out of device memory"); return cleanup(MLN_ERR_HIP); }
+  int rc = rowmin_wide_prepare(ctx, y, m, same ? nullptr : x, n, d, prep);
+  if (rc == MLN_OK) rc = launch_split_wide(ctx, x, n, d, xs, xx, nullptr, 1, prep);
+  if (rc == MLN_OK) rc = launch_split_wide(ctx, y, m, d, ys, same ? nullptr : yy, yyf, 2, prep);
+  if (same) yy = xx;
+  if (rc == MLN_OK) rc = launch_max_norm(ctx, yy, m, ymax);
+  if (rc != MLN_OK) return cleanup(rc);
+  if (hipMemsetAsync(nflag, 0, sizeof(int), ctx->stream) != hipSuccess) return cleanup(MLN_ERR_HIP);
+  rc = launch_rowmin_wide(ctx, xs, n, ys, m, d, yyf, self_offset, 1, m1, m2, arg);
+  if (rc == MLN_OK) rc = launch_nn_certify_wide(ctx, x, n, y, m, d, xx, yy, m2, arg, ymax, self_offset, prep, out, nflag, flagged);
+  if (rc != MLN_OK) return cleanup(rc);
+  int cnt = 0;
+  if (hipMemcpyAsync(&cnt, nflag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess) return cleanup(mln_hip_fail(ctx, hipGetLastError(), "nn certify", __FILE__, __LINE__));
+  if (std::getenv("MELLON_AMD_TRACE"))
+    std::fprintf(stderr, "[trace] nn_distances (wide): the sweep left %d of %lld rows open\n", cnt, (long long)n);
+  if (cnt > 0) {
+    // the uncertified rows: exact fp64 search, each with its own excluded candidate
+    double *xg = nullptr, *og = nullptr;
+    int64_t* excl = nullptr;
+    if (!alloc((void**)&xg, sizeof(double) * (size_t)cnt * d) || !alloc((void**)&og, sizeof(double) * cnt) ||
+        !alloc((void**)&excl, sizeof(int64_t) * cnt)) { mln_set_error(ctx, "nn_distances: out of device memory"); return cleanup(MLN_ERR_HIP); }
+    hipLaunchKernelGGL(k_gather_rows_excl, dim3((unsigned)cnt), dim3(64), 0, ctx->stream, x, d, flagged, cnt, self_offset, xg, excl);
+    rc = launch_nn_distances_exact(ctx, xg, cnt, y, m, d, 0, excl, og);
+    if (rc != MLN_OK) return cleanup(rc);
+    hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, og, flagged, cnt, out);
+  }
+  if (hipGetLastError() != hipSuccess) return cleanup(MLN_ERR_HIP);
+  ctx->nn_last[0] = 4.0;
+  ctx->nn_last[1] = (double)cnt;
+  ctx->nn_last[2] = (double)cnt;
+  return cleanup(MLN_OK);
+}
+
+int nn_distances_wide(mln_ctx* ctx, const double* x, int64_t n, const double* y, int64_t m, int d, int64_t self_offset, double* out) {
+  return nn_search_wide(ctx, x, n, y, m, d, self_offset, out);
 }
 
 int kmeans_lloyd_from(mln_ctx* ctx, const double* x, int64_t n, int32_t d, int64_t m, int32_t max_iter, const double* init, double* centers);   // kmeans.hip

@@ -75,8 +75,9 @@ KMEANS_DEVICE_INIT = "device"
 
 
 def landmarks_backend(n, d, n_landmarks):
-    """Where compute_landmarks runs by default: "hip" when n * n_landmarks exceeds KMEANS_DEVICE_THRESHOLD and d <= 64."""
-    return "hip" if (n * n_landmarks > KMEANS_DEVICE_THRESHOLD and d <= 64) else "sklearn"
+    """Where compute_landmarks runs by default: "hip" when n * n_landmarks exceeds KMEANS_DEVICE_THRESHOLD and d <= 256
+    (the feature range of the device k-means and of the covariance program)."""
+    return "hip" if (n * n_landmarks > KMEANS_DEVICE_THRESHOLD and d <= 256) else "sklearn"
 
 
 def compute_landmarks(x, gp_type=None, n_landmarks=DEFAULT_N_LANDMARKS, random_state=DEFAULT_RANDOM_SEED,
@@ -84,7 +85,8 @@ def compute_landmarks(x, gp_type=None, n_landmarks=DEFAULT_N_LANDMARKS, random_s
     """k-means centroids (reference parameters.py:243-291).  backend "sklearn" is the reference's
     own call (bit-identical landmarks); "hip" is k-means++ / Lloyd on the device (mln_kmeans: same
     algorithm family; its seeding is the library's own or, with KMEANS_DEVICE_INIT = "sklearn", sklearn's); None picks "hip" when n * n_landmarks exceeds
-    KMEANS_DEVICE_THRESHOLD (where sklearn takes minutes) and d <= 64.  x may be HBM-resident (a DeviceArray);
+    KMEANS_DEVICE_THRESHOLD (where sklearn takes minutes) and d <= 256.  Cells with more than 64 features are always seeded
+    by the library's own draws: the sklearn-compatible seeding stops at 64 features.  x may be HBM-resident (a DeviceArray);
     ctx: the device context to run on (default: the calling thread's)."""
     if n_landmarks == 0:
         return None
@@ -104,6 +106,10 @@ def compute_landmarks(x, gp_type=None, n_landmarks=DEFAULT_N_LANDMARKS, random_s
     if backend == "hip":
         import os
         init = os.environ.get("MELLON_AMD_KMEANS_INIT", KMEANS_DEVICE_INIT)
+        if init == "sklearn" and x.shape[1] > 64:
+            logger.info(f"sklearn-compatible k-means seeding stops at 64 features (the cells have {x.shape[1]}): "
+                        "using the device seeding.")
+            init = "device"
         return (ctx or _lib.default_context()).kmeans(x if on_device else np.ascontiguousarray(x, dtype=np.float64), n_landmarks,
                                                       seed=random_state if random_state is not None else DEFAULT_RANDOM_SEED,
                                                       init=init)
